@@ -11,11 +11,21 @@ libnepmi.so (nepmi_run_nve).  Workload at N = 1: BASELINE.json configs[2], PbTe 
 (`replicate 16 16 16` of the 250-atom cell of examples/gpumd_static, model examples/nep_train/nep.txt),
 rattled, 300 K Maxwell velocities, dt = 1 fs.  Inputs are resident in HBM before the timed region.
 
-One JSON line is printed by rank 0 (see the contract in the task description); it also carries
+One JSON line is printed by rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step, ...); it also carries
   "roofline":     dominant force kernel vs the HBM roofline, durations from HIP events recorded on
                   the engine's own stream inside the timed region
+
+A plain run sets up, warms up (with the 4-step probe that picks the kernel whose events ride in the timed region), times
+the K steps and prints the line.  Everything else runs only with --full, after the clock: the instrumented pass behind
+the full per-kernel table, gpu_state, extra_measurements (the rebuild-inclusive segment, thermo every step, the per-call
+sequence, other model shapes and families; N > 1: the strong-scaling leg and the overlap x ghosts matrix) and
   "cpu_baseline": the reference's own NEP_CPU (oracle/_ref) timed on this box's host cores on a
                   bounded 16,000-atom sample of the same crystal (rank 0, N = 1 only)
+
+--dump-outputs DIR writes what the timed run loop returned after its last step (single-GPU path): position, velocity,
+force, potential and virial of a fixed sample of at most DUMP_ATOMS atoms (all of them when there are fewer; the
+sample is drawn with DUMP_SEED, rows in ascending atom order, SoA planes as the caller holds them) and the thermo row,
+as DIR/<name>.npy in float64.  The inputs are seeded, so two builds run with the same arguments compare array by array.
 """
 import argparse
 import subprocess
@@ -40,6 +50,8 @@ METRIC = {"pbte": "atom-steps/sec, NEP PbTe NVE (nep4 2 Te Pb, examples/nep_trai
           "si_tersoff": "atom-steps/sec, Tersoff-1989 Si NVE (BASELINE config 2: examples/gpumd_benchmark/Si_Tersoff)"}
 KERNEL_NAMES = ["gather_skin_check", "radial_descriptor", "angular_descriptor", "ann", "angular_partial_force",
                 "force_assemble", "velocity_verlet", "list_rebuild"]
+DUMP_ATOMS = 1 << 18  # --dump-outputs: 19 float64 per atom -> at most 40 MB
+DUMP_SEED = 20251016
 
 
 def _oracle_helpers():
@@ -460,6 +472,28 @@ def gpu_state():
     return out
 
 
+def dump_outputs(outdir, n, arrays, thermo):
+    """--dump-outputs: arrays = {name: (device tensor of k planes of n float64, k)}; the same seeded atom sample from
+    every plane, and the thermo rows of the timed run"""
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    m = min(n, DUMP_ATOMS)
+    idx = np.arange(n) if m == n else np.sort(np.random.default_rng(DUMP_SEED).choice(n, m, replace=False))
+    t_idx = None
+    files = {}
+    for name, (t, k) in arrays.items():
+        if t_idx is None:
+            t_idx = torch.from_numpy(idx).to(t.device)
+        a = t.view(k, n).index_select(1, t_idx).cpu().numpy().astype(np.float64)
+        files[name] = a[0] if k == 1 else a
+    files["thermo"] = np.asarray(thermo, dtype=np.float64)
+    total = sum(a.nbytes for a in files.values())
+    if total > 64 << 20:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the 64 MB bound" % total)
+    for name, a in files.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
 def measure_extra(workload, reps, steps, warmup, dev, generic=False):
     """One more measurement AFTER the clock of the bench line has stopped (config.extra_measurements): its own engine, the
     same protocol (inputs resident, warm-up, K steps between synchronisations, HIP events on the dominant kernel inside
@@ -600,9 +634,11 @@ def run_decomposed(args, world, rank, dev, model, label, h_block, typ, x, mass, 
     STAGE = "decomposed[%s]: instrumented pass" % scaling
     st = md.engine_stats(with_lists=True)
     th = md.thermo()
-    md.engine_set_timing(1)
-    md.run(ens, dt, max(10, min(steps, 40)), *t_args)  # instrumented pass for the per-kernel table, outside the clock
-    st_all = md.engine_stats(with_lists=False)
+    st_all = None
+    if args.full:
+        md.engine_set_timing(1)
+        md.run(ens, dt, max(10, min(steps, 40)), *t_args)  # instrumented pass for the per-kernel table, outside the clock
+        st_all = md.engine_stats(with_lists=False)
     md.engine_set_timing(0)
     info = md.info()
     # A checksum of the decomposed forces: every atom's force gathered on rank 0 and compared with ONE-domain evaluation of the
@@ -766,10 +802,15 @@ def main():
     ap.add_argument("--reps", type=int, nargs=3, default=[16, 16, 16], help="replicate na nb nc of the 250-atom cell")
     ap.add_argument("--workload", default="pbte", choices=["pbte", "pbte_ortho", "carbon", "carbon2024", "unep", "si_tersoff"],
                     help="pbte = BASELINE config 3 (the bench line); the others are extra single-GPU measurements")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the clock, also measure what the headline does not need: the per-kernel table, gpu_state, "
+                         "extra_measurements and the CPU / reference baselines (a plain run only times the K steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed steps computed in their last step as DIR/<name>.npy (single-GPU path)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU / reference baselines")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip extra_measurements (config 2, the rebuild-inclusive PbTe segment, the config 4/5 model families; "
-                         "N > 1: the strong-scaling leg), all timed after the bench line's clock")
+                    help="with --full: skip extra_measurements (config 2, the rebuild-inclusive PbTe segment, the config 4/5 model "
+                         "families; N > 1: the strong-scaling leg), all timed after the bench line's clock")
     ap.add_argument("--decomposed", action="store_true",
                     help="run the N > 1 code path (the C++ domain-decomposed driver) even on one GPU, to measure its overhead")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
@@ -788,6 +829,8 @@ def main():
     if args.cpu_worker is not None:  # one instance of the all-cores CPU aggregate, no GPU involved
         cpu_worker(args.cpu_worker)
         return
+    if args.dump_outputs and (args.gpus > 1 or args.decomposed):
+        ap.error("--dump-outputs writes the single-GPU run loop's arrays; it does not apply to --gpus N > 1 or --decomposed")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)
     rank = int(os.environ.get("RANK", "0"))
@@ -878,7 +921,7 @@ def bench(args):
         if world > 1 and backend != "nccl" and out is not None:
             out["functional_only"] = ("ranks share %d GPU(s) over the TCP transport (host staging): the protocol of the N-GPU run, "
                                       "not its performance" % torch.cuda.device_count())
-        if world > 1 and args.scaling == "weak" and not args.no_extras:
+        if world > 1 and args.scaling == "weak" and args.full and not args.no_extras:
             # after the clock: the SAME 1,024,000-atom system as the N = 1 line cut over the N GPUs (strong scaling), with the
             # force checksum against a one-domain evaluation on rank 0
             try:
@@ -968,11 +1011,16 @@ def bench(args):
     th = eng.run_nve(h, t_type, t_mass, dt, args.steps, t_x, t_v, t_pe, t_f, t_w, thermo_every=args.steps)
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:  # before anything else steps the arrays on
+        dump_outputs(args.dump_outputs, n, {"position": (t_x, 3), "velocity": (t_v, 3), "force": (t_f, 3), "potential": (t_pe, 1),
+                                            "virial": (t_w, 9)}, th)
     st = eng.stats(with_lists=True)
-    eng.set_timing(1)
-    extra = max(10, min(args.steps, 60))
-    eng.run_nve(h, t_type, t_mass, dt, extra, t_x, t_v, t_pe, t_f, t_w, thermo_every=extra)
-    st_all = eng.stats(with_lists=False)
+    st_all, extra = None, 0
+    if args.full:
+        eng.set_timing(1)
+        extra = max(10, min(args.steps, 60))
+        eng.run_nve(h, t_type, t_mass, dt, extra, t_x, t_v, t_pe, t_f, t_w, thermo_every=extra)
+        st_all = eng.stats(with_lists=False)
     eng.set_timing(0)
 
     t_el = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -1019,10 +1067,12 @@ def bench(args):
             "step_hbm_frac": b_step * (n * args.steps / elapsed) / (HBM_PEAK_GBS * 1e9),
             "kernels": kern,
             "kernels_note": "the step's longest force kernel (found by a 4-step instrumented probe before the clock): HIP events inside "
-                            "the timed region; the others: an instrumented pass of %d further steps" % extra,
-            "gpu_state": gpu_state(),
+                            "the timed region; the others: " + ("an instrumented pass of %d further steps" % extra if args.full else
+                                                                "not measured (bench.py --full)"),
             "thermo_last": [float(v) for v in th[-1]] if len(th) else None,
         }
+        if args.full:
+            out["gpu_state"] = gpu_state()
         if args.workload == "pbte":
             # the path is FP32-VALU/gather bound, so the step is also priced against the
             # FP32 vector peak with the survey's FLOP count of the reference algorithm (8e4 per atom-step)
@@ -1034,7 +1084,7 @@ def bench(args):
                                 "note": "frac_own prices the operations this engine executes (counted from its kernels for "
                                         "this model shape; ~1.31 Verlet candidates per radial neighbour); the survey figure is "
                                         "the reference algorithm's count and only says how much of it was avoided"}
-        if world == 1 and not args.no_extras and not args.no_cpu_baseline and args.workload == "pbte":
+        if world == 1 and args.full and not args.no_extras and not args.no_cpu_baseline and args.workload == "pbte":
             # After the clock: (a) the same engine for further 100-step segments until one of them contains a list rebuild
             # (at 300 K one rebuild per ~100 steps): the rebuild-inclusive rate; (b) BASELINE config 2 (Si 13,824 atoms,
             # Tersoff-1989, FP64) on its own engine.  Each carries its own roofline object.
@@ -1172,7 +1222,7 @@ def bench(args):
                            "WITH rebuilds and thermo: these are the same engine on the same system, measured after the clock" % int(st.num_rebuild - reb0))
             out["like_for_like"] = lfl
             out["extra_measurements"] = extras
-        if world == 1 and not args.no_cpu_baseline and args.workload == "pbte":
+        if world == 1 and args.full and not args.no_cpu_baseline and args.workload == "pbte":
             with _stdout_to_stderr():
                 out["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
                 del eng  # the reference needs the HBM of a 1 M-atom run of its own
@@ -1181,7 +1231,7 @@ def bench(args):
                 if ref_gpu:
                     ref_gpu["speedup_of_this_engine"] = value / ref_gpu["value"]
                     out["cpu_baseline"]["reference_gpu_same_box"] = ref_gpu
-        if world == 1 and not args.no_cpu_baseline and tersoff:
+        if world == 1 and args.full and not args.no_cpu_baseline and tersoff:
             with _stdout_to_stderr():
                 out["cpu_baseline"] = cpu_baseline_tersoff(nep_txt, h, typ, x0, mass, vel0, args.cpu_seconds)
         # the last key of the line: what a reader who only sees the END of this (long) line needs

@@ -1,11 +1,12 @@
 # on the GPU box: for each variant library run the bench and print its kernel table
 cd /root/repo
+OUT=${OUT:-bench_out}; mkdir -p "$OUT"  # where the bench lines and logs go
 cp gpumd_amd/lib/libnepmi.so /tmp/libnepmi_product.so
 for v in gpumd_amd/lib/variants/libnepmi_*.so; do
   name=$(basename $v .so); name=${name#libnepmi_}
   cp $v gpumd_amd/lib/libnepmi.so
-  python bench.py --no-cpu-baseline $AB_ARGS > gpurun_out/ab_$name.json 2> gpurun_out/ab_$name.err
-  python - gpurun_out/ab_$name.json $name <<'PY'
+  python bench.py --full --no-cpu-baseline $AB_ARGS > $OUT/ab_$name.json 2> $OUT/ab_$name.err
+  python - $OUT/ab_$name.json $name <<'PY'
 import json,sys
 try:
     d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

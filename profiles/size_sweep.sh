@@ -1,12 +1,13 @@
 # size sweep of the PbTe NVE line + the Si Tersoff config-2 line: bash profiles/size_sweep.sh <tag>
 cd /root/repo
+OUT=${OUT:-bench_out}; mkdir -p "$OUT"  # where the bench lines and logs go
 T=$1
 for r in "4 4 4" "8 8 8" "12 12 12" "16 16 16"; do
   n=$(echo $r | tr ' ' x)
-  python bench.py --no-cpu-baseline --reps $r --steps 400 --warmup 50 > gpurun_out/sweep_${T}_$n.json 2> gpurun_out/sweep_${T}_$n.err
+  python bench.py --full --no-cpu-baseline --reps $r --steps 400 --warmup 50 > $OUT/sweep_${T}_$n.json 2> $OUT/sweep_${T}_$n.err
 done
-python bench.py --workload si_tersoff --steps 2000 --warmup 200 --cpu-seconds 6 > gpurun_out/sweep_${T}_si.json 2> gpurun_out/sweep_${T}_si.err
-for f in gpurun_out/sweep_${T}_*.json; do
+python bench.py --full --workload si_tersoff --steps 2000 --warmup 200 --cpu-seconds 6 > $OUT/sweep_${T}_si.json 2> $OUT/sweep_${T}_si.err
+for f in $OUT/sweep_${T}_*.json; do
 python - $f <<'PY'
 import json,sys
 try:
