@@ -1579,7 +1579,7 @@ struct HipBackend {
     return (size_t)fused_lds_layout<S>(md).total;
   }
   template <class S>
-  void launch_angular_fused(int slot, int64_t n, const ModelD& md, const Bufs& b, int export_qfp, float* img, bool build)
+  void launch_angular_fused(int slot, int64_t n, const ModelD& md, const Bufs& b, int export_qfp, float* img, bool build, bool pair_trip)
   {
     AngularFusedBody<S> body{md, b, export_qfp, nullptr};
     if (build) {
@@ -1595,6 +1595,14 @@ struct HipBackend {
                          // against 2.290 -- the lockstep waiting it removes is not what the kernel's time is made of (vector issue of the heaviest
                          // wavefront of a workgroup, which the sort makes no lighter).  Off.
 #endif
+    // (the same image: the two forms differ in their record loops only.  Up to four channels per lane: with five and more the kernel
+    // already spills at 256 VGPRs and the trips' second set of (g, g') adds to the scratch -- carbon 156 -> 168 B; kFusedTripMaxChannels)
+    if constexpr (FusedShape<S>::NLOC <= kFusedTripMaxChannels) {
+      if (pair_trip) {
+        launch_lds_pairs<NEPMI_AFU_BLOCK, AngularFusedBody<S, 1>, NEPMI_AFU_SORT != 0>(slot, n, AngularFusedBody<S, 1>{md, b, export_qfp, img});
+        return;
+      }
+    }
     launch_lds_pairs<NEPMI_AFU_BLOCK, AngularFusedBody<S>, NEPMI_AFU_SORT != 0>(slot, n, body);
   }
 

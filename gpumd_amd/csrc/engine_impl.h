@@ -1639,7 +1639,7 @@ private:
         fused_img_floats_ = need;
         fused_img_stale_ = true;
       }
-      be_.template launch_angular_fused<S>(kSlotAngular, N_, md_, b_, export_qfp, fused_img_, fused_img_stale_);
+      be_.template launch_angular_fused<S>(kSlotAngular, N_, md_, b_, export_qfp, fused_img_, fused_img_stale_, ang_pair_trip_);
       fused_img_stale_ = false;
     }
   }
@@ -1840,6 +1840,7 @@ public:
     use_rmask_ = o.use_rmask_;
     use_csync_ = o.use_csync_;
     ang_fused_ = o.ang_fused_;
+    ang_pair_trip_ = o.ang_pair_trip_;
     brick_force_ = o.brick_force_;
     loop_ctx_ = o.loop_ctx_;
     scatter_disabled_ = o.scatter_disabled_;
@@ -2265,6 +2266,11 @@ public:
   bool last_scatter_form() const { return last_scatter_form_; }
   // 1 (default): angular descriptor, ANN and partial angular forces in one kernel where ang_fused_active() allows; 0: separately
   void set_angular_fused(bool on) { ang_fused_ = on; }
+  // 1 (default): the record loops of the fused angular kernel in trips of two records, the radial part of a record evaluated by
+  // one lane of the pair (nep_bodies.h: angular_s_sums_trip, pairs_from_G_trip); 0: one record per trip, on both lanes.  Same bits.
+  void set_angular_pair_trip(bool on) { ang_pair_trip_ = on; }
+  // ... where the shape has at most four angular channels per lane (nep_fused.h: kFusedTripMaxChannels; beyond, the trips cost scratch)
+  bool ang_pair_trip_active() const { return ang_pair_trip_ && (model_.n_max_angular + 2) / 2 <= 4; }
   // 1: ... and the scatter-form force assembly in the same kernel, one workgroup per brick (nep_brick.h); 0 (default)
   void set_brick_force(bool on) { brick_force_ = on; }
   static constexpr bool has_brick_force() { return B::kHasBrickForce; }
@@ -2398,7 +2404,8 @@ public:
       s += " force=one_kernel_per_brick(descriptor+ann+partial_forces+lds_scatter_of_own_halves,lane_pairs)";
     else if (last_ang_fused_)
       s += last_ang_window_ ? " angular=descriptor+ann+partial_forces_in_one_kernel(lane_pairs,sums_in_registers,type_sorted,window_of_4_types)"
-                            : " angular=descriptor+ann+partial_forces_in_one_kernel(lane_pairs,sums_in_registers)";
+                            : (ang_pair_trip_active() ? " angular=descriptor+ann+partial_forces_in_one_kernel(lane_pairs,sums_in_registers,two_record_trips)"
+                                              : " angular=descriptor+ann+partial_forces_in_one_kernel(lane_pairs,sums_in_registers)");
     else if (fuse_ann_active())
       s += " ann=fused_with_angular_descriptor(packed_fp32,no_mfma)";
     else if (ann_mode_ != 0 && b_.ann_img && (model_.num_types <= 4 || b_.skip_atab))
@@ -2479,6 +2486,9 @@ private:
   bool virial_local_ = false;    // the virial planes of the last force evaluation hold the own-half form (exact_virials)
   double hard_factor_ = 4.0;     // set_scatter_guard: hard limit of runs whose flagged steps stand = factor x guard band
   bool ang_fused_ = true;        // set_angular_fused
+  // set_angular_pair_trip; NEPMI_ANGULAR_PAIR_TRIP=0 in the environment: the default of engines no caller can reach (the local
+  // engines of a decomposed run's ranks, tests/test_fused_pair_trip.py)
+  bool ang_pair_trip_ = !(std::getenv("NEPMI_ANGULAR_PAIR_TRIP") && std::atoi(std::getenv("NEPMI_ANGULAR_PAIR_TRIP")) == 0);
   bool brick_force_ = false;     // set_brick_force (off: measured slower, see nep_brick.h)
   bool last_brick_ = false;      // the last force evaluation ran the per-brick force kernel
   bool brick_pending_ = false;   // ... and its partial forces / radial table have not been written to HBM since (materialise_for_gather)

@@ -1760,6 +1760,106 @@ NEPMI_HD void angular_s_sums(const ModelD& m, const Bufs& b, int64_t k, int t1, 
   }
 }
 
+// The same sums of a LANE PAIR in trips of two records (fused angular kernel, nep_fused.h).  What a record costs before any
+// channel is touched -- distance, envelope, Chebyshev basis -- does not depend on the lane, yet in angular_s_sums both lanes
+// of the pair evaluate it for every record.  Here a trip takes rows a and a + 1: lane `part` loads row a + part only, evaluates
+// that row's radial part once and contracts it to g_n for its own channels and for the partner's; the partner's values and
+// the unit vector cross the pair as quad_perm DPP moves.  Every g_n is the same fma chain on the same operands as in
+// angular_s_sums, and the rows enter the sums in row order, so the sums are bit-identical.  A lane whose own row is a padding
+// row (kNullRecord) or lies behind an odd last row computes on arbitrary numbers that nothing reads; a trip of two such rows is
+// skipped.  All exchanges sit in control flow that is uniform across the pair.
+template <class S, class LP>
+NEPMI_HD void angular_s_sums_trip(const ModelD& m, const Bufs& b, int64_t k, int t1, LP cang, int part, float* s)
+{
+  static_assert(S::fixed, "compiled shapes only");
+  constexpr int NLOC = (S::NA + 2) / 2;
+  const int64_t N = b.N;
+  const float rc1 = m.rc_a[t1];
+  const int cstride = cang_stride(m);
+  f2 s2[NLOC * kHarmPairs];
+#pragma unroll
+  for (int a = 0; a < NLOC * kHarmPairs; ++a)
+    s2[a] = bc2(0.0f);
+  const int na = b.nn_angstep[k];
+  const F4* __restrict__ acomp = b.acomp + k;
+  F4 e_next;
+  e_next.x = e_next.y = e_next.z = 1.0f;
+  e_next.w = kNullRecord;
+  if (part < na)
+    e_next = acomp[(int64_t)part * N];
+  for (int a = 0; a < na; a += 2) {
+    const F4 e = e_next;
+    e_next.w = kNullRecord;
+    if (a + 2 + part < na)
+      e_next = acomp[(int64_t)(a + 2 + part) * N]; // in flight while this trip is processed
+    const int wA = NEPMI_PAIR_EVEN(e.w), wB = NEPMI_PAIR_ODD(e.w);
+    if (wA == kNullRecord && wB == kNullRecord)
+      continue;
+    // ---- this lane's row: the radial part, once per pair of lanes ----
+    const int t2 = e.w != kNullRecord ? (int)((unsigned)e.w >> kIdxBits) : 0;
+    const float x = e.x, y = e.y, z = e.z;
+    float d, dinv;
+    dist_and_inv(dot3f(x, x, y, y, z, z), d, dinv);
+    const float rc = m.uniform_rc ? m.rc_a_max : (rc1 + m.rc_a[t2]) * 0.5f;
+    const float rcinv = fast_rcp(rc);
+    float fc;
+    cutoff_fc(rcinv, d, fc);
+    float fn[S::KA + 1];
+    basis_fn<S::KA>(rcinv, d, fc, fn);
+    const float ux = x * dinv, uy = y * dinv, uz = z * dinv;
+    LP c = cang + (t1 * m.T + t2) * cstride;
+    float gm[NLOC], go[NLOC]; // g_n of this row: this lane's channels, the partner's channels
+#pragma unroll
+    for (int i = 0; i < NLOC; ++i) {
+      // (the last channel of an even n_max exists on lane 0 only: the other lane's copy is formed from row n_max and never read)
+      const int nm = part + 2 * i <= S::NA ? part + 2 * i : S::NA, no = (part ^ 1) + 2 * i <= S::NA ? (part ^ 1) + 2 * i : S::NA;
+      float g0 = 0.0f, g1 = 0.0f;
+#pragma unroll
+      for (int kk = 0; kk <= S::KA; ++kk) {
+        g0 = fmaf(fn[kk], c[nm * (S::KA + 1) + kk], g0);
+        g1 = fmaf(fn[kk], c[no * (S::KA + 1) + kk], g1);
+      }
+      gm[i] = g0;
+      go[i] = g1;
+    }
+    // ---- rows a (the even lane's) and a + 1 (the odd lane's), in this order, into this lane's sums ----
+    auto row = [&](const float* g, float rx, float ry, float rz) __attribute__((always_inline)) {
+      f2 bh[kHarmPairs];
+      harmonics_pairs(rx, ry, rz, bh);
+#pragma unroll
+      for (int i = 0; i < NLOC; ++i) {
+        if (part + 2 * i > S::NA)
+          break;
+        const f2 g2 = bc2(g[i]);
+#pragma unroll
+        for (int q = 0; q < kHarmPairs; ++q)
+          s2[i * kHarmPairs + q] = vfma(g2, bh[q], s2[i * kHarmPairs + q]);
+      }
+    };
+    float gA[NLOC], gB[NLOC];
+#pragma unroll
+    for (int i = 0; i < NLOC; ++i) {
+      const float gp = NEPMI_PAIR_XCHG(go[i]); // the partner's row, this lane's channels
+      gA[i] = part ? gp : gm[i];
+      gB[i] = part ? gm[i] : gp;
+    }
+    const float uxA = NEPMI_PAIR_EVEN(ux), uyA = NEPMI_PAIR_EVEN(uy), uzA = NEPMI_PAIR_EVEN(uz);
+    const float uxB = NEPMI_PAIR_ODD(ux), uyB = NEPMI_PAIR_ODD(uy), uzB = NEPMI_PAIR_ODD(uz);
+    if (wA != kNullRecord)
+      row(gA, uxA, uyA, uzA);
+    if (wB != kNullRecord)
+      row(gB, uxB, uyB, uzB);
+  }
+  const int hp[kNumHarm] = NEPMI_HARM_PAIR_INIT;
+#pragma unroll
+  for (int i = 0; i < NLOC; ++i)
+#pragma unroll
+    for (int q = 0; q < kHarmPairs; ++q) {
+      s[i * kNumHarm + hp[2 * q]] = s2[i * kHarmPairs + q].x;
+      s[i * kNumHarm + hp[2 * q + 1]] = s2[i * kHarmPairs + q].y;
+    }
+}
+
 // angular part of find_descriptor (nep.cu:549-640) on the compacted angular pair records:
 // no gathers, no geometry, every lane of the wavefront has real work in every iteration.
 // LDS image of the per-atom ANN for the fused descriptor + ANN kernel (AngularDescBody::fuse_ann), behind c_ang:
@@ -2129,6 +2229,74 @@ struct AngularForceBody {
     }
   };
 
+  // ZBL is per pair and independent of the channel split: the lanes take alternate neighbours.  A pair beyond
+  // the outer cutoff contributes exact zeros (fc = 0): it is skipped, and with it four exponentials, a sine, a
+  // cosine and a power -- for the alloy models that is nearly every angular pair.
+  NEPMI_HD void zbl_terms(int t1, int t2, int zi, float pzi, float x, float y, float z, float d, float dinv, float* zf, float* zv,
+                          float& zpe) const
+  {
+    float zbl_r2 = 0.0f;
+    const float* zbl_p10 = nullptr;
+    if (m.zbl_flexible) {
+      const int ta = t1 < t2 ? t1 : t2, tb = t1 < t2 ? t2 : t1;
+      const int zidx = ta * m.T - (ta * (ta - 1)) / 2 + (tb - ta);
+      zbl_p10 = m.zbl_para + 10 * zidx;
+      zbl_r2 = zbl_p10[1];
+    } else if (m.zbl_rco) { // type-wise outer cutoff, inner cutoff 0 (nep.cu:935-941)
+      zbl_r2 = m.zbl_rco[t1 * m.T + t2];
+    } else {
+      zbl_r2 = m.zbl_rc_outer;
+    }
+    if (!(d < zbl_r2))
+      return;
+    const int zj = m.atomic_number[t2];
+    const float a_inv = (pzi + powf((float)zj, 0.23f)) * 2.134563f;
+    const float zizj = 14.399645f * (float)zi * (float)zj;
+    float f, fp;
+    if (m.zbl_flexible)
+      zbl_pair(zbl_p10, zizj, a_inv, 0.0f, 0.0f, d, dinv, f, fp);
+    else if (m.zbl_rco)
+      zbl_pair(nullptr, zizj, a_inv, 0.0f, zbl_r2, d, dinv, f, fp);
+    else
+      zbl_pair(nullptr, zizj, a_inv, m.zbl_rc_inner, m.zbl_rc_outer, d, dinv, f, fp);
+    const float f2 = fp * dinv * 0.5f;
+    const float fx = x * f2, fy = y * f2, fz = z * f2; // f12; f21 = -f12
+    zf[0] += fx + fx;
+    zf[1] += fy + fy;
+    zf[2] += fz + fz;
+    zv[0] -= x * fx;
+    zv[1] -= y * fy;
+    zv[2] -= z * fz;
+    zv[3] -= x * fy;
+    zv[4] -= x * fz;
+    zv[5] -= y * fz;
+    zpe += f * 0.5f;
+  }
+  // the lanes' ZBL sums of an atom joined and written (lane 0)
+  template <int PARTS>
+  NEPMI_HD void zbl_store(int64_t k, int part, float* zf, float* zv, float zpe) const
+  {
+    const int64_t N = b.N;
+    if (m.zbl_enabled && PARTS > 1) {
+#pragma unroll
+      for (int d = 0; d < 3; ++d)
+        zf[d] += NEPMI_PAIR_XCHG(zf[d]);
+#pragma unroll
+      for (int d = 0; d < 6; ++d)
+        zv[d] += NEPMI_PAIR_XCHG(zv[d]);
+      zpe += NEPMI_PAIR_XCHG(zpe);
+    }
+    if (m.zbl_enabled && part == 0) {
+#pragma unroll
+      for (int d = 0; d < 3; ++d)
+        b.zbl[(int64_t)d * N + k] = zf[d];
+#pragma unroll
+      for (int d = 0; d < 6; ++d)
+        b.zbl[(int64_t)(3 + d) * N + k] = zv[d];
+      b.zbl[(int64_t)9 * N + k] = zpe;
+    }
+  }
+
   // The pair loop: partial forces f12 of this step's angular pairs from the atom's adjoint table G (this lane's channels,
   // harmonic order), + ZBL.  Also the tail of the fused descriptor + ANN + force kernel (nep_fused.h), which arrives here
   // with G built from sums that never left the registers.
@@ -2257,66 +2425,132 @@ struct AngularForceBody {
       out.w = 0;
       sink(a, part, out, e);
 
-      // ZBL is per pair and independent of the channel split: the lanes take alternate neighbours.  A pair beyond
-      // the outer cutoff contributes exact zeros (fc = 0): it is skipped, and with it four exponentials, a sine, a
-      // cosine and a power -- for the alloy models that is nearly every angular pair.
-      float zbl_r2 = 0.0f;
-      const float* zbl_p10 = nullptr;
-      if (m.zbl_enabled) {
-        if (m.zbl_flexible) {
-          const int ta = t1 < t2 ? t1 : t2, tb = t1 < t2 ? t2 : t1;
-          const int zidx = ta * m.T - (ta * (ta - 1)) / 2 + (tb - ta);
-          zbl_p10 = m.zbl_para + 10 * zidx;
-          zbl_r2 = zbl_p10[1];
-        } else if (m.zbl_rco) { // type-wise outer cutoff, inner cutoff 0 (nep.cu:935-941)
-          zbl_r2 = m.zbl_rco[t1 * m.T + t2];
-        } else {
-          zbl_r2 = m.zbl_rc_outer;
+      if (m.zbl_enabled && (PARTS == 1 || (a % PARTS) == part))
+        zbl_terms(t1, t2, zi, pzi, x, y, z, d, dinv, zf, zv, zpe);
+    }
+    zbl_store<PARTS>(k, part, zf, zv, zpe);
+  }
+
+  // The pair loop of a LANE PAIR in trips of two records (see angular_s_sums_trip): lane `part` loads row a + part, evaluates
+  // that row's distance, envelope, basis and derivative once, and contracts them to (g_n, g_n') for its own channels and for the
+  // partner's.  Each lane then forms its channels' share of (w, v) for its own row and, from the partner's (g, g') and unit
+  // vector, for the partner's row; the shares of a row meet on the lane that owns it, which finishes and writes that row -- and
+  // takes its ZBL term, the alternation of pairs_from_G.  No result depends on the order of the two rows, so each lane does its
+  // own first: no selects.  Same operations on the same operands as pairs_from_G (the two-term sums across the pair commute):
+  // bit-identical rows.
+  template <class LP, class Sink>
+  NEPMI_HD void pairs_from_G_trip(int64_t k, int part, LP cang, int t1, const float* G, Sink&& sink) const
+  {
+    static_assert(S::fixed, "compiled shapes only");
+    constexpr int NLOC = (S::NA + 2) / 2;
+    const int64_t N = b.N;
+    const float rc1 = m.rc_a[t1];
+    const int cstride = cang_stride(m);
+    f2 G2[NLOC * kHarmPairs];
+    {
+      const int hp[kNumHarm] = NEPMI_HARM_PAIR_INIT;
+#pragma unroll
+      for (int i = 0; i < NLOC; ++i)
+#pragma unroll
+        for (int q = 0; q < kHarmPairs; ++q)
+          G2[i * kHarmPairs + q] = mk2(G[i * kNumHarm + hp[2 * q]], G[i * kNumHarm + hp[2 * q + 1]]);
+    }
+    float zf[3] = {0, 0, 0}, zv[6] = {0, 0, 0, 0, 0, 0}, zpe = 0.0f;
+    float pzi = 0.0f;
+    int zi = 0;
+    if (m.zbl_enabled) {
+      zi = m.atomic_number[t1];
+      pzi = powf((float)zi, 0.23f);
+    }
+    // this lane's share of (w, v) of one row from that row's (g, g') of this lane's channels and its unit vector
+    auto share = [&](const f2* gg, float rx, float ry, float rz, float& w, float& vx, float& vy, float& vz) __attribute__((always_inline)) {
+      f2 P2[kHarmPairs], Q2[kHarmPairs];
+#pragma unroll
+      for (int q = 0; q < kHarmPairs; ++q)
+        P2[q] = Q2[q] = bc2(0.0f);
+#pragma unroll
+      for (int i = 0; i < NLOC; ++i) {
+        if (part + 2 * i > S::NA)
+          break;
+        const f2 g2 = bc2(gg[i].x), gp2 = bc2(gg[i].y);
+#pragma unroll
+        for (int q = 0; q < kHarmPairs; ++q) {
+          P2[q] = vfma(G2[i * kHarmPairs + q], g2, P2[q]);
+          Q2[q] = vfma(G2[i * kHarmPairs + q], gp2, Q2[q]);
         }
       }
-      if (m.zbl_enabled && d < zbl_r2 && (PARTS == 1 || (a % PARTS) == part)) {
-        const int zj = m.atomic_number[t2];
-        const float a_inv = (pzi + powf((float)zj, 0.23f)) * 2.134563f;
-        const float zizj = 14.399645f * (float)zi * (float)zj;
-        float f, fp;
-        if (m.zbl_flexible)
-          zbl_pair(zbl_p10, zizj, a_inv, 0.0f, 0.0f, d, dinv, f, fp);
-        else if (m.zbl_rco)
-          zbl_pair(nullptr, zizj, a_inv, 0.0f, zbl_r2, d, dinv, f, fp);
-        else
-          zbl_pair(nullptr, zizj, a_inv, m.zbl_rc_inner, m.zbl_rc_outer, d, dinv, f, fp);
-        const float f2 = fp * dinv * 0.5f;
-        const float fx = x * f2, fy = y * f2, fz = z * f2; // f12; f21 = -f12
-        zf[0] += fx + fx;
-        zf[1] += fy + fy;
-        zf[2] += fz + fz;
-        zv[0] -= x * fx;
-        zv[1] -= y * fy;
-        zv[2] -= z * fz;
-        zv[3] -= x * fy;
-        zv[4] -= x * fz;
-        zv[5] -= y * fz;
-        zpe += f * 0.5f;
+      harmonics_contract_pairs(rx, ry, rz, P2, Q2, w, vx, vy, vz);
+    };
+
+    const int na = b.nn_angstep[k];
+    const F4* __restrict__ acomp = b.acomp + k;
+    F4 e_next;
+    e_next.x = e_next.y = e_next.z = 1.0f;
+    e_next.w = kNullRecord;
+    if (part < na)
+      e_next = acomp[(int64_t)part * N];
+    for (int a = 0; a < na; a += 2) {
+      const F4 e = e_next;
+      e_next.w = kNullRecord;
+      if (a + 2 + part < na)
+        e_next = acomp[(int64_t)(a + 2 + part) * N];
+      const bool own = e.w != kNullRecord, partner = NEPMI_PAIR_XCHG(e.w) != kNullRecord;
+      if (!own && !partner)
+        continue; // (padding rows: no partial force is written for them, their aslot is the sentinel)
+      const int t2 = own ? (int)((unsigned)e.w >> kIdxBits) : 0;
+      const float x = e.x, y = e.y, z = e.z;
+      float d, dinv;
+      dist_and_inv(dot3f(x, x, y, y, z, z), d, dinv);
+      const float rc = m.uniform_rc ? m.rc_a_max : (rc1 + m.rc_a[t2]) * 0.5f;
+      const float rcinv = fast_rcp(rc);
+      float fc, fcp;
+      cutoff_fc_fcp(rcinv, d, fc, fcp);
+      float fn[S::KA + 1], fnp[S::KA + 1];
+      basis_fn_fnp<S::KA>(rcinv, d, fc, fcp, fn, fnp);
+      LP c = cang + (t1 * m.T + t2) * cstride;
+      const float ux = x * dinv, uy = y * dinv, uz = z * dinv;
+      f2 ffp[S::KA + 1];
+#pragma unroll
+      for (int kk = 0; kk <= S::KA; ++kk)
+        ffp[kk] = mk2(fn[kk], fnp[kk]);
+      f2 ggm[NLOC], ggr[NLOC]; // (g, g') of this lane's channels: of its own row; of the partner's row (received)
+#pragma unroll
+      for (int i = 0; i < NLOC; ++i) {
+        // (the last channel of an even n_max exists on lane 0 only: the other lane's copy is formed from row n_max and never read)
+        const int nm = part + 2 * i <= S::NA ? part + 2 * i : S::NA, no = (part ^ 1) + 2 * i <= S::NA ? (part ^ 1) + 2 * i : S::NA;
+        f2 g0 = bc2(0.0f), g1 = bc2(0.0f);
+#pragma unroll
+        for (int kk = 0; kk <= S::KA; ++kk) {
+          g0 = vfma(ffp[kk], bc2(c[nm * (S::KA + 1) + kk]), g0);
+          g1 = vfma(ffp[kk], bc2(c[no * (S::KA + 1) + kk]), g1);
+        }
+        ggm[i] = g0;
+        ggr[i] = mk2(NEPMI_PAIR_XCHG(g1.x), NEPMI_PAIR_XCHG(g1.y));
+      }
+      const float px = NEPMI_PAIR_XCHG(ux), py = NEPMI_PAIR_XCHG(uy), pz = NEPMI_PAIR_XCHG(uz);
+      float w = 0.0f, vx = 0.0f, vy = 0.0f, vz = 0.0f;     // this lane's share of its own row
+      float pw = 0.0f, pvx = 0.0f, pvy = 0.0f, pvz = 0.0f; // ... of the partner's row
+      if (own)
+        share(ggm, ux, uy, uz, w, vx, vy, vz);
+      if (partner)
+        share(ggr, px, py, pz, pw, pvx, pvy, pvz);
+      w += NEPMI_PAIR_XCHG(pw);
+      vx += NEPMI_PAIR_XCHG(pvx);
+      vy += NEPMI_PAIR_XCHG(pvy);
+      vz += NEPMI_PAIR_XCHG(pvz);
+      if (own) {
+        const float udv = ux * vx + uy * vy + uz * vz;
+        F4 out;
+        out.x = ux * w + (vx - ux * udv) * dinv;
+        out.y = uy * w + (vy - uy * udv) * dinv;
+        out.z = uz * w + (vz - uz * udv) * dinv;
+        out.w = 0;
+        sink(a + part, 0, out, e);
+        if (m.zbl_enabled)
+          zbl_terms(t1, t2, zi, pzi, x, y, z, d, dinv, zf, zv, zpe);
       }
     }
-    if (m.zbl_enabled && PARTS > 1) {
-#pragma unroll
-      for (int d = 0; d < 3; ++d)
-        zf[d] += NEPMI_PAIR_XCHG(zf[d]);
-#pragma unroll
-      for (int d = 0; d < 6; ++d)
-        zv[d] += NEPMI_PAIR_XCHG(zv[d]);
-      zpe += NEPMI_PAIR_XCHG(zpe);
-    }
-    if (m.zbl_enabled && part == 0) {
-#pragma unroll
-      for (int d = 0; d < 3; ++d)
-        b.zbl[(int64_t)d * N + k] = zf[d];
-#pragma unroll
-      for (int d = 0; d < 6; ++d)
-        b.zbl[(int64_t)(3 + d) * N + k] = zv[d];
-      b.zbl[(int64_t)9 * N + k] = zpe;
-    }
+    zbl_store<2>(k, part, zf, zv, zpe);
   }
 };
 

@@ -23,9 +23,13 @@
 #if defined(__HIP_DEVICE_COMPILE__)
 #define NEPMI_WAVE_ANY(pred) (__any((int)(pred)))
 #define NEPMI_PAIR_XCHG(v) (nepmi::quad_xor<1>(v)) // value held by the partner lane (lanes 2i, 2i+1)
+#define NEPMI_PAIR_EVEN(v) (nepmi::pair_lane<0>(v)) // value held by the even lane of the pair, on both lanes
+#define NEPMI_PAIR_ODD(v) (nepmi::pair_lane<1>(v))  // ... by the odd lane
 #else
 #define NEPMI_WAVE_ANY(pred) (pred)
 #define NEPMI_PAIR_XCHG(v) (v) // host loops run one lane per atom: never reached with PARTS > 1
+#define NEPMI_PAIR_EVEN(v) (v)
+#define NEPMI_PAIR_ODD(v) (v)
 #endif
 
 namespace nepmi {
@@ -50,6 +54,17 @@ template <int MSK>
 __device__ __forceinline__ unsigned quad_xor(unsigned v)
 {
   return (unsigned)quad_xor<MSK>((int)v);
+}
+// Value held by lane 2i + ODD of the lane pair (2i, 2i+1), on both of its lanes: quad_perm [0,0,2,2] / [1,1,3,3].
+template <int ODD>
+__device__ __forceinline__ int pair_lane(int v)
+{
+  return __builtin_amdgcn_update_dpp(0, v, ODD ? 0xF5 : 0xA0, 0xF, 0xF, true);
+}
+template <int ODD>
+__device__ __forceinline__ float pair_lane(float v)
+{
+  return __int_as_float(pair_lane<ODD>(__float_as_int(v)));
 }
 #endif
 

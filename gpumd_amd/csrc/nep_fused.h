@@ -45,6 +45,9 @@ struct FusedShape {
   }
 };
 
+// most angular channels per lane for which the kernel takes its record loops in trips of two records (AngularFusedBody<S, 1>)
+constexpr int kFusedTripMaxChannels = 4;
+
 struct FusedLdsLayout {
   int wstride, off_w, off_b0, off_w1, off_c, off_qs, total;
 };
@@ -71,7 +74,10 @@ NEPMI_HD FusedLdsLayout fused_lds_layout(const ModelD& m, int TW = 0)
   return a;
 }
 
-template <class S>
+// TRIP = 1: the two record loops in trips of two records, each record's radial part evaluated by one lane of the pair instead of
+// by both (angular_s_sums_trip, pairs_from_G_trip: bit-identical results).  TRIP = 0: the one-record loops that the separate
+// kernels run as well (engine option "angular_pair_trip"; the type-window and per-brick kernels keep them).
+template <class S, int TRIP = 0>
 struct AngularFusedBody {
   ModelD m;
   Bufs b;
@@ -207,7 +213,10 @@ struct AngularFusedBody {
     adjoint_in_place(part, Fp, s);
     const AngularForceBody<S> af{m, b, 1};
     if (NEPMI_AFU_ABL != 2) {
-      af.template pairs_from_G<2>(k, part, cang, t1, s, typename AngularForceBody<S>::F12Store{b.f12 + k, b.N});
+      if constexpr (TRIP)
+        af.pairs_from_G_trip(k, part, cang, t1, s, typename AngularForceBody<S>::F12Store{b.f12 + k, b.N});
+      else
+        af.template pairs_from_G<2>(k, part, cang, t1, s, typename AngularForceBody<S>::F12Store{b.f12 + k, b.N});
     } else if (s[3] + s[NLOC * kNumHarm - 1] == 12345.0f) {
       b.pe_i[k] = s[5] + s[NLOC * kNumHarm - 2];
     }
@@ -267,7 +276,10 @@ struct AngularFusedBody {
 
     // ---- sums of this lane's channels (angular_s_sums: what AngularDescBody runs) ----
     if (NEPMI_AFU_ABL != 3) {
-      angular_s_sums<S, 2>(m, b, k, t1, cang, part, s);
+      if constexpr (TRIP)
+        angular_s_sums_trip<S>(m, b, k, t1, cang, part, s);
+      else
+        angular_s_sums<S, 2>(m, b, k, t1, cang, part, s);
     } else {
 #pragma unroll
       for (int i = 0; i < NLOC * kNumHarm; ++i)

@@ -343,6 +343,11 @@ class NEP:
         (option "angular_fused")"""
         self.set_option("angular_fused", 1 if on else 0)
 
+    def set_angular_pair_trip(self, on=True):
+        """record loops of the fused angular kernel in trips of two records, one radial evaluation per record and lane pair
+        (default), or one record per trip on both lanes (option "angular_pair_trip"); bit-identical results"""
+        self.set_option("angular_pair_trip", 1 if on else 0)
+
     def describe(self):
         """the kernel forms the last force evaluation ran (counted rules of the engine, as text)"""
         import ctypes as C

@@ -500,6 +500,13 @@ int nepmi_engine_set_virial_mode(nepmi_engine* e, int mode);
  *       types, fewer than 9 angular channels) -- the sums s_{n,lm} stay in the registers across the ANN and become the adjoint table in
  *       place, where the separate kernels evaluate them twice; 0: the separate kernels.  Same results up to the summation order of
  *       the ANN's dot products (tests/test_gpu_parity.py).
+ *   "angular_pair_trip": the two record loops of that kernel in trips of two records: value = 1 (default) -- each lane of the pair
+ *       evaluates the radial part (distance, envelope, basis, derivative) of ONE of the two records and hands the partner that
+ *       record's (g_n, g_n') for the partner's channels and its unit vector through quad_perm DPP moves; 0: one record per trip,
+ *       its radial part evaluated on both lanes.  The same operations on the same operands: bit-identical results
+ *       (tests/test_fused_pair_trip.py).  Shapes with at most four angular channels per lane (n_max_angular <= 6): with more, the
+ *       trips' second set of (g, g') spills (carbon: 156 -> 168 B of scratch) and the one-record loops stay, as they do in the
+ *       type-window and per-brick forms of the kernel.
  *   "brick_force": ... and the scatter-form force assembly (find_force_radial, nep.cu:661-772; gpu_find_force_many_body, potential.cu:170-297) in
  *       the SAME kernel, one 512-thread workgroup per brick behind the radial pass: value = 1 where the fused angular kernel and the
  *       scatter form both apply, on shapes with two register-resident atom types, in single-domain engines; the partial forces and
