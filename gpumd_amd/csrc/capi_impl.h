@@ -580,6 +580,8 @@ int nepmi_engine_set_option(nepmi_engine* e, const char* name, double value)
     eng.set_angular_fused(iv != 0);
   else if (n == "angular_pair_trip")
     eng.set_angular_pair_trip(iv != 0);
+  else if (n == "fold_seam")
+    eng.set_fold_seam(iv != 0);
   else if (n == "brick_force") {
     if (iv != 0 && !eng.has_brick_force())
       return fail(NEPMI_ERR_ARG, "option 'brick_force': the per-brick force kernel is not part of this build (make BRICK=1)");

@@ -1387,7 +1387,7 @@ struct HipBackend {
   void launch_force_scatter(int slot, int64_t nb, int first, int64_t natoms, const WinStage& ws2, const ModelD& md, int* halo,
                             const unsigned* fmap, int fold_rows, bool outputs, int mode, int fold_lo, int fold_hi, const int* frz)
   {
-    const ForceScatterBody<S> body{ws2, md, frz, reinterpret_cast<I4*>(halo), first};
+    const ForceScatterBody<S> body{ws2, md, frz, reinterpret_cast<I3*>(halo), first};
     const int64_t grid = (nb + 7) / 8 * 8;
     const bool t = timed(slot);
     if (t)
@@ -1453,11 +1453,28 @@ struct HipBackend {
       NEPMI_HIP_CHECK(hipGetLastError());
     }
     if (fold_lo <= fold_hi && natoms > 0) {
-      const ForceFoldBody fold{ws2.b, md, ws2.lay.wmax, fold_rows, fmap, reinterpret_cast<const I4*>(halo), fold_lo, fold_hi};
+      const ForceFoldBody fold{ws2.b, md, ws2.lay.wmax, fold_rows, fmap, reinterpret_cast<const I3*>(halo), fold_lo, fold_hi};
       const int64_t fgrid = ((natoms + 255) / 256 + 7) / 8 * 8;
       hipLaunchKernelGGL((nepmi_kernel<256, ForceFoldBody>), dim3((unsigned)fgrid), dim3(256), 0, stream, fold, natoms, frz);
       NEPMI_HIP_CHECK(hipGetLastError());
     }
+    if (t)
+      timer_stop(timing->slot[slot]);
+  }
+  // The fold of the last launch_force_scatter (called with fold_lo > fold_hi) and the integrator pass behind it as one pass over
+  // the atoms (nep_scatter.h: FoldSeamBody); not under `frozen`: the body looks at the word itself, like ResidentStepBody
+  void launch_fold_seam(int slot, int64_t natoms, const Bufs& b, const ModelD& md, int wmax, const int* halo, const unsigned* fmap,
+                        int fold_rows, const ResidentStepBody& rs, bool write_f)
+  {
+    if (natoms <= 0)
+      return;
+    const FoldSeamBody body{ForceFoldBody{b, md, wmax, fold_rows, fmap, reinterpret_cast<const I3*>(halo), 0, 2}, rs, write_f ? 1 : 0};
+    const int64_t grid = ((natoms + 255) / 256 + 7) / 8 * 8;
+    const bool t = timed(slot);
+    if (t)
+      timer_start(timing->slot[slot]);
+    hipLaunchKernelGGL((nepmi_kernel<256, FoldSeamBody>), dim3((unsigned)grid), dim3(256), 0, stream, body, natoms, nullptr);
+    NEPMI_HIP_CHECK(hipGetLastError());
     if (t)
       timer_stop(timing->slot[slot]);
   }
@@ -1657,7 +1674,7 @@ struct HipBackend {
                           const unsigned* fmap, int fold_rows, bool outputs, const float* img, const int* frz)
   {
     if constexpr (S::fixed && S::TS == 2) {
-      const BrickForceBody<S> body{ForceScatterBody<S>{ws2, md, frz, reinterpret_cast<I4*>(halo), -1},
+      const BrickForceBody<S> body{ForceScatterBody<S>{ws2, md, frz, reinterpret_cast<I3*>(halo), -1},
                                    AngularFusedBody<S>{md, ws2.b, 0, img}};
       const int64_t grid = (nb + 7) / 8 * 8;
       const size_t lds_bytes = (brick_lds_bytes<S>(md, ws2.lay.wmax) + 15) / 16 * 16;
@@ -1684,7 +1701,7 @@ struct HipBackend {
       if (t)
         timer_start(timing->slot[slot_fold]);
       if (natoms > 0) {
-        const ForceFoldBody fold{ws2.b, md, ws2.lay.wmax, fold_rows, fmap, reinterpret_cast<const I4*>(halo), 0, 2};
+        const ForceFoldBody fold{ws2.b, md, ws2.lay.wmax, fold_rows, fmap, reinterpret_cast<const I3*>(halo), 0, 2};
         const int64_t fgrid = ((natoms + 255) / 256 + 7) / 8 * 8;
         hipLaunchKernelGGL((nepmi_kernel<256, ForceFoldBody>), dim3((unsigned)fgrid), dim3(256), 0, stream, fold, natoms, frz);
         NEPMI_HIP_CHECK(hipGetLastError());

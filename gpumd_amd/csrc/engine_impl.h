@@ -737,6 +737,16 @@ public:
     const bool temp_ramp = model_.temperature_model && ens != kNve && t1 != t2;
     if (model_.temperature_model && ens != kNve && temperature_ != t1)
       set_temperature(t1);
+    // (nothing is deferred across calls: an exception that left the loop between a deferring force evaluation and the pass that
+    // takes the assembly must not reach the next call)
+    tersoff_deferred_ = tersoff_defer_ = false;
+    fold_deferred_ = fold_defer_ = false;
+    last_fold_seam_ = false;
+    auto fold_seam = [&](const ResidentStepBody& rs, bool write_f) { // the fold of the step just evaluated + rs as one pass
+      if constexpr (B::kHasScatter)
+        be_.launch_fold_seam(kSlotVV, N_, b_, md_, win_.wmax, halo_, fmap_, fold_rows_, rs, write_f);
+      fold_deferred_ = false;
+    };
     bool resume_after_vv1 = false; // the pre-force phase of `step` has already run (replay after a rebuild)
     bool kick2_pending = false;    // NVE: the second half-kick of step - 1 rides on this step's first pass
     while (step < nsteps) {
@@ -755,6 +765,8 @@ public:
         } else if (tersoff_deferred_) {
           be_.template launch<64>(kSlotVV, N_, TersoffSeamBody{TersoffAssembleBody{b_, tb_}, ResidentStepBody{box_, b_, dt, 1, 1, tag_of(step)}});
           tersoff_deferred_ = false;
+        } else if (fold_deferred_) {
+          fold_seam(ResidentStepBody{box_, b_, dt, 1, 1, tag_of(step)}, false);
         } else {
           be_.template launch<256>(kSlotVV, N_, ResidentStepBody{box_, b_, dt, kick2_pending ? 1 : 0, 1, tag_of(step)});
         }
@@ -768,9 +780,19 @@ public:
       step_outputs_ = record || last; // per-atom energies and virials: read at thermo records and at the exit only
       b_.trip_tag = tag_of(step);     // (scatter form: a force beyond its fixed-point guard band freezes the loop at this step)
       tersoff_defer_ = NEPMI_TERSOFF_SEAM && model_.kind == 1 && ens == kNve && !record && !last;
+      // scatter form: the fold rides in the next pass over the atoms -- the first pass of the next step, or on a record / last step
+      // the second half-kick below (the other ensembles, whose passes differ, keep the separate fold)
+      // (after a veto the separate kernels for kSeamBackoffSteps steps: a veto costs a look at the flags and the steps enqueued
+      // behind it, which a system that stays above the bound must not pay step after step)
+      fold_defer_ = fold_seam_ && seam_backoff_ == 0 && B::kHasScatter && model_.kind == 0 && ens == kNve;
+      if (seam_backoff_ > 0)
+        --seam_backoff_;
       force_kernels(kPhaseAll, frozen);
       tersoff_defer_ = false;
+      fold_defer_ = false;
       b_.trip_tag = 0;
+      if (last_scatter_form_)
+        last_fold_seam_ = fold_deferred_;
       // A thermo record does not stop the pipeline: find_thermo's eight numbers go to row `rec` of a device buffer (a 64-byte copy on the
       // stream) and all rows come to the host when the loop ends -- the reference reduces thermo on EVERY step (ensemble_nve.cu:59-95),
       // so a record must not cost a host round trip.  (Measured, r6v: thermo every step 1.287 ms with or without the per-record
@@ -780,7 +802,10 @@ public:
       if (ens == kNve && !record && !last) {
         kick2_pending = true; // fused into the next step's pass over the atoms
       } else {
-        be_.template launch<256>(kSlotVV, N_, ResidentStepBody{box_, b_, dt, 1, 0, 0});
+        if (fold_deferred_)
+          fold_seam(ResidentStepBody{box_, b_, dt, 1, 0, 0}, true);
+        else
+          be_.template launch<256>(kSlotVV, N_, ResidentStepBody{box_, b_, dt, 1, 0, 0});
         if (ens == kBer) {
           thermo_now();
           if (1.0 / tcoup > 1.0e-5) { // ensemble_ber.cu:223
@@ -825,10 +850,28 @@ public:
         }
       }
       if (trip) {
-        step = handle_trip(trip, step);
-        calm_since = step;
+        const bool veto = flags[kFlagSeamVeto] != 0;
+        if (veto) { // (only a scatter kernel whose fold was deferred sets it, and only where no skin trip had frozen its step)
+          be_.memset(b_.flags + kFlagSeamVeto, 0, sizeof(int));
+          ++num_seam_vetoes_;
+          seam_backoff_ = kSeamBackoffSteps;
+        }
+        if (veto && !flags[kFlagRange]) {
+          // A window sum too large for the seam and nothing in the guard band: the state stands frozen right behind the first pass of
+          // that step, on the lists it was evaluated with.  Only its force evaluation is due again, with the separate fold -- no
+          // export, no rebuild, no import: a rebuild here would be one that the separate kernels never make, and with it the
+          // rounding of another list generation.  (The radial and angular kernels run a second time on the same positions and
+          // lists: the same bits.)
+          num_discarded += step - ((int64_t)trip - 1) + 1;
+          be_.memset(b_.flags + kFlagMoved, 0, sizeof(int));
+          step = (int64_t)trip - 1;
+        } else {
+          step = handle_trip(trip, step);
+          calm_since = step;
+        }
         resume_after_vv1 = true;
         tersoff_deferred_ = false; // (the frozen step's pass had taken the assembly of the step before it; what was enqueued since ran as no-ops)
+        fold_deferred_ = false;
         continue;
       }
       ++step;
@@ -1512,9 +1555,9 @@ private:
       check_overflow(flags);
     }
     if (win2_ok_ && b_.aslot) {
-      // scatter-form force assembly: one halo row per brick (the window sums its workgroup leaves for ForceFoldBody, 16 bytes
+      // scatter-form force assembly: one halo row per brick (the window sums its workgroup leaves for ForceFoldBody, 12 bytes
       // per window slot) and, per atom, the table of the windows that hold it (nep_scatter.h: FoldMapBody)
-      const size_t need = (size_t)num_bricks_ * (size_t)win_.wmax * 4;
+      const size_t need = (size_t)num_bricks_ * (size_t)win_.wmax * kHaloRowWords;
       if (need > halo_cap_) {
         dfree(halo_);
         halo_ = nullptr;
@@ -1841,6 +1884,7 @@ public:
     use_csync_ = o.use_csync_;
     ang_fused_ = o.ang_fused_;
     ang_pair_trip_ = o.ang_pair_trip_;
+    fold_seam_ = o.fold_seam_;
     brick_force_ = o.brick_force_;
     loop_ctx_ = o.loop_ctx_;
     scatter_disabled_ = o.scatter_disabled_;
@@ -2154,6 +2198,14 @@ private:
                                            halo_, fmap_, fold_rows_, step_outputs_, list_mode(), 0, 1, frozen);
       assembly_pending_ = true;
       pending_outputs_ = step_outputs_;
+    } else if (fold_defer_ && !b_.level) {
+      // (a single-domain NVE run loop: the fold rides in the next pass over the atoms, FoldSeamBody; the scatter kernel vouches for
+      // its window sums -- Bufs::seam_row_limit, with the guard band as it stands for THIS evaluation -- or freezes the step)
+      WinStage wsd = ws2;
+      wsd.b.seam_row_limit = std::max(1, b_.fold_guard / std::max(1, fold_rows_));
+      be_.template launch_force_scatter<S>(kSlotForce, num_bricks_, -1, N_, wsd, md_, halo_, fmap_, fold_rows_, step_outputs_,
+                                           list_mode(), 1, 0, frozen);
+      fold_deferred_ = true;
     } else {
       be_.template launch_force_scatter<S>(kSlotForce, num_bricks_, -1, N_, ws2, md_, halo_, fmap_, fold_rows_, step_outputs_,
                                            list_mode(), 0, 2, frozen);
@@ -2271,6 +2323,10 @@ public:
   void set_angular_pair_trip(bool on) { ang_pair_trip_ = on; }
   // ... where the shape has at most four angular channels per lane (nep_fused.h: kFusedTripMaxChannels; beyond, the trips cost scratch)
   bool ang_pair_trip_active() const { return ang_pair_trip_ && (model_.n_max_angular + 2) / 2 <= 4; }
+  // 1 (default): single-domain NVE run loops fold the scatter form's window sums inside the integrator pass behind them
+  // (nep_scatter.h: FoldSeamBody); 0: ForceFoldBody and ResidentStepBody as two launches.  Same bits, also across a step that a
+  // window sum too large for the seam sends back to the separate kernels (run_md: no list rebuild for it).
+  void set_fold_seam(bool on) { fold_seam_ = on; }
   // 1: ... and the scatter-form force assembly in the same kernel, one workgroup per brick (nep_brick.h); 0 (default)
   void set_brick_force(bool on) { brick_force_ = on; }
   static constexpr bool has_brick_force() { return B::kHasBrickForce; }
@@ -2419,9 +2475,12 @@ public:
     s += (last_scatter_form_ && last_mask_form_)   ? " radial_list=inside_bits_over_the_verlet_words"
          : (last_scatter_form_ && last_sync_form_) ? " radial_list=wave_synchronous_words"
                                                    : " radial_list=compacted";
-    s += last_scatter_form_ ? " force_assembly=lds_scatter_of_own_halves(fixed_point)+fold" :
+    s += last_scatter_form_ ? (last_fold_seam_ ? " force_assembly=lds_scatter_of_own_halves(fixed_point)+fold_in_integrator_pass"
+                                               : " force_assembly=lds_scatter_of_own_halves(fixed_point)+fold") :
          last_rows_form_ ? " force_assembly=table_rows_in_lds"
                          : (last_fpj_form_ ? " force_assembly=neighbour_half_from_fp_rows" : " force_assembly=table_rows_gathered");
+    if (num_seam_vetoes_ > 0)
+      s += " seam_vetoes=" + std::to_string(num_seam_vetoes_);
     if (tile_ok_)
       s += " bricks=" + std::to_string(num_bricks_) + " window_slots=" + std::to_string(win_.wmax);
     return s;
@@ -2503,6 +2562,14 @@ private:
   bool last_sync_form_ = false;
   int guard_delay_ = 0;          // set_scatter_guard_delayed
   int guard_delay_next_ = 0;
+  // set_fold_seam; NEPMI_FOLD_SEAM=0 in the environment: the default of engines no caller can reach
+  bool fold_seam_ = !(std::getenv("NEPMI_FOLD_SEAM") && std::atoi(std::getenv("NEPMI_FOLD_SEAM")) == 0);
+  bool fold_defer_ = false;       // this force evaluation leaves the scatter form's fold to the next pass over the atoms (run loop, NVE)
+  bool fold_deferred_ = false;    // ... and that fold is still due
+  static constexpr int kSeamBackoffSteps = 256;
+  int seam_backoff_ = 0;          // steps that still fold separately after a window sum too large for that pass (flags[kFlagSeamVeto])
+  int64_t num_seam_vetoes_ = 0;   // times that happened (describe)
+  bool last_fold_seam_ = false;   // the last run-loop step left its fold to the integrator pass
   bool tersoff_defer_ = false;    // this force evaluation leaves the Tersoff assembly to the next pass over the atoms (run loop, NVE)
   bool tersoff_deferred_ = false; // ... and that assembly is still due
   int64_t calm_steps_ = 0;        // run-loop steps since the last list rebuild, across calls (run_md: how often the host looks at the flags)
@@ -2520,7 +2587,7 @@ private:
   bool assembly_pending_ = false, pending_outputs_ = true;
   bool outputs_stale_ = false;   // the last force evaluation left the energy / virial planes as they were
   bool scatter_disabled_ = false; // a pair half left the fixed-point guard band of the scatter form: gather form from then on
-  int* halo_ = nullptr;          // [bricks][wmax][4] window sums of the scatter form (fixed point)
+  int* halo_ = nullptr;          // [bricks][wmax][kHaloRowWords] window sums of the scatter form (fixed point)
   size_t halo_cap_ = 0;
   unsigned* fmap_ = nullptr;     // [fold_rows_][cap_] the windows that hold each atom (brick << 13 | slot)
   int fold_rows_ = 8;

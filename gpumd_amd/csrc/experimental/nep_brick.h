@@ -387,14 +387,8 @@ nepmi_brick_force_kernel(const BrickForceBody<S> body, const int64_t nbricks)
   for (int64_t k = a0 + (tid >> 1); k < a1; k += kWinThreads)
     brick_force_atom<S, OUT>(body, brick, k, tid & 1, lds, lay);
   __syncthreads();
-  {
-    NEPMI_LDS(const I3)* acc = (NEPMI_LDS(const I3)*)(lds + lay.off_acc());
-    I4* __restrict__ out = body.sc.halo + (size_t)brick * lay.wmax;
-    for (int i = tid; i < (NEPMI_BRK_ABL == 2 ? 0 : lay.wmax); i += kBrickThreads) {
-      const I3 v = acc[i];
-      out[i] = I4{v.x, v.y, v.z, 0};
-    }
-  }
+  if (NEPMI_BRK_ABL != 2)
+    halo_write_out<kBrickThreads>(body.sc.st.b, lds + lay.off_acc(), body.sc.halo + (size_t)brick * lay.wmax, lay.wmax, tid);
 }
 
 } // namespace nepmi

@@ -86,6 +86,8 @@ enum FlagSlot {
   kFlagMaxWindow = 5, kFlagMaxBrick = 6, kFlagMaxCell = 7, kFlagNumBoundary = 8,
   kFlagOutlier = 9, // an atom sits more than half a cell outside the box along an open direction
   kFlagFoldRows = 10, // scratch word of FoldMapBody: the most windows an atom lies in
+  kFlagSeamVeto = 11, // a scatter kernel whose fold was left to the next integrator pass (nep_scatter.h: FoldSeamBody) wrote a window
+                      // sum too large for that: the step is frozen and re-run with the separate fold (Bufs::seam_row_limit)
   kNumFlags = 12
 };
 // bits of flags[kFlagOverflow]: 1, 2, 4 list capacities; 8 non-finite coordinates; 16 a force beyond the HARD limit of the
@@ -234,9 +236,14 @@ struct Bufs {
   int trip_tag;  // != 0: a speculatively enqueued step of a single-domain run loop -- a force beyond the fixed-point guard band of the
                  // scatter-form assembly freezes the loop at this step like a skin trip (flags[kFlagMoved] = tag), and the host
                  // re-runs the step in the gather form
+  int seam_row_limit;    // > 0: the fold of this step's window sums rides in the next pass over the atoms, which cannot be re-run: a
+                         // scatter kernel that writes a sum of this size or more (fixed point) says so (flags[kFlagSeamVeto]) and
+                         // freezes the step (trip_tag); below it no fold can reach its guard band (limit = fold_guard / rows)
   int compact_all;       // 1: every atom with level >= 1 writes its compact radial list (the scatter form walks the lists of the
                          // atoms that have descriptors, the gather form those of the atoms that receive forces)
 };
+
+constexpr int kHaloRowWords = 3; // words per window slot of the scatter form's halo rows: {fx, fy, fz} in fixed point
 
 // planes of Bufs::fo
 constexpr int kOutPe = 0, kOutF = 1, kOutW = 4, kOutPlanes = 13;

@@ -13,7 +13,7 @@
 // LOCAL (LDS atomics, no global atomic) and DETERMINISTIC: the accumulators are 32-bit fixed point (2^-22 eV/A), integer adds
 // commute, so the sums do not depend on the order the lanes arrive in and a second call is bit-identical; +g and -g are the
 // same integer, so the total force is zero to the last bit.  The workgroup then writes its window accumulator to its own row
-// of the halo buffer (plain coalesced 16-byte stores, {fx, fy, fz, 0} per window slot), and ForceFoldBody adds, for every atom,
+// of the halo buffer (plain coalesced 16-byte stores of the 12-byte rows {fx, fy, fz}), and ForceFoldBody adds, for every atom,
 // the entries of the (normally eight) windows its cell lies in -- tabulated per atom at the list rebuild (FoldMapBody), a fixed
 // order, no atomics anywhere outside the LDS.
 //
@@ -33,6 +33,7 @@
 #pragma once
 #include <climits>
 #include "nep_window.h"
+#include "nep_md.h"
 
 #ifndef NEPMI_FS_MT_VEC
 #define NEPMI_FS_MT_VEC 1 // many-type form: coefficient blocks padded to 4 (odd) floats and read with 16-byte ds_reads (r4j: UNEP-v1 1 M atoms, force assembly 1.02 -> 0.78 ms); 0 = element-wise, odd stride
@@ -78,7 +79,7 @@ struct ForceScatterBody {
   WinStage st; // lay.compact == 1 (static window layout)
   ModelD m;
   const int* frozen;
-  I4* halo;  // [brick][wmax] {fx, fy, fz, 0} in fixed point
+  I3* halo; // [brick][wmax] {fx, fy, fz} in fixed point
   int first; // workgroup w runs brick brick_order[first + w] (first < 0: brick w): the boundary bricks of a decomposed run first,
              // so that the ghosts' partial forces can travel while the interior bricks run (DistT, reverse-mode ghosts)
 };
@@ -95,6 +96,38 @@ __device__ __forceinline__ void scatter_range_trip(const Bufs& b)
 __device__ __forceinline__ void scatter_range_hard(const Bufs& b)
 {
   atomicOr(&b.flags[kFlagOverflow], kOverflowRangeHard);
+}
+
+// The window sums of a workgroup, LDS -> its halo row: what ForceFoldBody gathers.  12-byte rows on both sides, so the row is one
+// contiguous copy in 16-byte pieces (wmax is a multiple of 64).  Bufs::seam_row_limit > 0: the fold of these sums rides in the
+// next integrator pass (FoldSeamBody), which advances the atoms as it folds and so cannot stop at a value in the guard band
+// the way the separate fold does; every sum below limit = fold_guard / rows keeps every fold of at most `rows` of them inside the
+// band, and a larger one freezes the step here, BEFORE that pass, for the host to re-run it with the separate kernels.
+template <int NT>
+__device__ __forceinline__ void halo_write_out(const Bufs& b, NEPMI_LDS(const char)* acc_bytes, I3* __restrict__ out, int wmax, int tid)
+{
+  NEPMI_LDS(const U4)* acc = (NEPMI_LDS(const U4)*)acc_bytes;
+  U4* __restrict__ o4 = reinterpret_cast<U4*>(out);
+  const int n4 = 3 * wmax / 4;
+  const unsigned lim = (unsigned)b.seam_row_limit;
+  if (lim == 0u) {
+    for (int i = tid; i < n4; i += NT)
+      o4[i] = acc[i];
+    return;
+  }
+  bool large = false;
+  for (int i = tid; i < n4; i += NT) {
+    const U4 v = acc[i];
+    o4[i] = v;
+    // |w| < lim  <=>  0 <= w + lim - 1 <= 2 lim - 2 (unsigned: everything else, INT_MIN included, lands above)
+    large = large || v.x + (lim - 1u) > 2u * lim - 2u || v.y + (lim - 1u) > 2u * lim - 2u || v.z + (lim - 1u) > 2u * lim - 2u ||
+            v.w + (lim - 1u) > 2u * lim - 2u;
+  }
+  if (large) {
+    atomicOr(&b.flags[kFlagSeamVeto], 1);
+    if (b.trip_tag)
+      atomicCAS(&b.flags[kFlagMoved], 0, b.trip_tag);
+  }
 }
 
 __device__ __forceinline__ void lds_add(NEPMI_LDS(int)* p, int v)
@@ -611,15 +644,8 @@ nepmi_force_scatter_kernel(const ForceScatterBody<S> body, const int64_t nbricks
   for (int64_t k = a0 + tid; k < a1; k += NT)
     force_scatter_atom<S, OUT, MODE>(body, brick, k, lds, lay);
   __syncthreads();
-  {
-    // the window sums, one 16-byte row per slot: what ForceFoldBody gathers
-    NEPMI_LDS(const I3)* acc = (NEPMI_LDS(const I3)*)(lds + lay.off_acc());
-    I4* __restrict__ out = body.halo + (size_t)brick * lay.wmax;
-    for (int i = tid; i < (NEPMI_FS_ABL == 5 ? 0 : lay.wmax); i += NT) {
-      const I3 v = acc[i];
-      out[i] = I4{v.x, v.y, v.z, 0};
-    }
-  }
+  if (NEPMI_FS_ABL != 5)
+    halo_write_out<NT>(b, lds + lay.off_acc(), body.halo + (size_t)brick * lay.wmax, lay.wmax, tid);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -929,14 +955,8 @@ __global__ void __launch_bounds__(kWinThreads * L) nepmi_force_scatter_mt_kernel
   for (int64_t k = a0 + tid / L; k < a1; k += kWinThreads)
     force_scatter_atom_mt<S, OUT, L, MODE>(body, brick, k, sub, lds, lay);
   __syncthreads();
-  {
-    NEPMI_LDS(const I3)* acc = (NEPMI_LDS(const I3)*)(lds + lay.off_acc());
-    I4* __restrict__ out = body.halo + (size_t)brick * lay.wmax;
-    for (int i = tid; i < (NEPMI_FS_ABL == 5 ? 0 : lay.wmax); i += NT) {
-      const I3 v = acc[i];
-      out[i] = I4{v.x, v.y, v.z, 0};
-    }
-  }
+  if (NEPMI_FS_ABL != 5)
+    halo_write_out<NT>(b, lds + lay.off_acc(), body.halo + (size_t)brick * lay.wmax, lay.wmax, tid);
 }
 
 // Which windows hold atom k, and where: entry r of the fold map = brick << 13 | slot, or kFoldNone.  A cell lies in the
@@ -1015,13 +1035,25 @@ struct ForceFoldBody {
   ModelD m;
   int wmax, rows;
   const unsigned* fmap;
-  const I4* halo;
+  const I3* halo;
   int lv_lo, lv_hi; // only atoms with level in [lv_lo, lv_hi] (the ghosts first when their forces travel during the interior bricks)
+  __device__ bool wanted(int lv) const { return !(lv < b.lvl_force || lv < lv_lo || lv > lv_hi); }
   __device__ void operator()(int64_t k) const
   {
     const int lv = b.lvl[k];
-    if (lv < b.lvl_force || lv < lv_lo || lv > lv_hi)
+    if (!wanted(lv))
       return;
+    double F[3];
+    fold(k, lv, F);
+    const int64_t N = b.N;
+    double* __restrict__ fo = b.fo + k;
+#pragma unroll
+    for (int d = 0; d < 3; ++d)
+      fo[(int64_t)(kOutF + d) * N] = F[d];
+  }
+  // the row walk of atom k (level lv) and its guard band; F in eV/A (also what FoldSeamBody hands to the integrator)
+  __device__ void fold(int64_t k, int lv, double* F) const
+  {
     const int64_t N = b.N;
     int s0 = 0, s1 = 0, s2 = 0; // (modular: the net of a window is what has to fit)
     unsigned g0 = 0u, g1 = 0u, g2 = 0u; // sum of |row| / 16 per component (up to 27 rows of < 2^31: no overflow): the shadow below
@@ -1031,10 +1063,10 @@ struct ForceFoldBody {
 #pragma unroll
       for (int u = 0; u < G; ++u)
         e[u] = r0 + u < rows ? fmap[(int64_t)(r0 + u) * N + k] : kFoldNone;
-      I4 h[G];
+      I3 h[G];
 #pragma unroll
       for (int u = 0; u < G; ++u) {
-        h[u] = I4{0, 0, 0, 0};
+        h[u] = I3{0, 0, 0};
         if (e[u] != kFoldNone)
           h[u] = halo[(size_t)(e[u] >> kFoldSlotBits) * wmax + (e[u] & ((1u << kFoldSlotBits) - 1u))];
       }
@@ -1061,16 +1093,45 @@ struct ForceFoldBody {
       if (b.fold_hard > 0 && (shadow || a0 >= b.fold_hard || a1 >= b.fold_hard || a2 >= b.fold_hard || s0 == INT_MIN || s1 == INT_MIN || s2 == INT_MIN))
         scatter_range_hard(b);
     }
-    double F[3] = {(double)s0 * kScatterInvScale, (double)s1 * kScatterInvScale, (double)s2 * kScatterInvScale};
+    F[0] = (double)s0 * kScatterInvScale;
+    F[1] = (double)s1 * kScatterInvScale;
+    F[2] = (double)s2 * kScatterInvScale;
     if (m.zbl_enabled && lv >= 2) {
 #pragma unroll
       for (int d = 0; d < 3; ++d)
         F[d] += (double)b.zbl[(int64_t)d * N + k];
     }
-    double* __restrict__ fo = b.fo + k;
+  }
+};
+
+// The fold and the integrator pass behind it as ONE pass over the atoms (single-domain NVE run loops): ForceFoldBody writes 24
+// bytes per atom that ResidentStepBody reads straight back, in the same internal order, and on a step that neither records
+// thermo data nor ends the call nothing else reads them -- here the three doubles stay in registers (the same expressions, so the
+// same bits), and Bufs::fo gets them only where write_f asks (record steps, the last step).  Like TersoffSeamBody: the fold reads
+// no positions or velocities, so the drift of one lane cannot disturb the fold of another.
+// A pass that advances the atoms cannot be re-run, and a value in the guard band means "re-run this step in the gather form":
+// the scatter kernel whose sums are folded here has vouched for them (halo_write_out, Bufs::seam_row_limit) -- with every
+// row below fold_guard / rows the checks in fold() cannot fire -- or has frozen the step, in which case this pass returns at once.
+struct FoldSeamBody {
+  ForceFoldBody fd;
+  ResidentStepBody rs;
+  int write_f;
+  __device__ void operator()(int64_t k) const
+  {
+    if (rs.frozen_now())
+      return;
+    const int lv = fd.b.lvl[k];
+    if (lv < 2 || !fd.wanted(lv))
+      return;
+    double F[3];
+    fd.fold(k, lv, F);
+    if (write_f) {
+      const int64_t N = fd.b.N;
 #pragma unroll
-    for (int d = 0; d < 3; ++d)
-      fo[(int64_t)(kOutF + d) * N] = F[d];
+      for (int d = 0; d < 3; ++d)
+        fd.b.fo[(int64_t)(kOutF + d) * N + k] = F[d];
+    }
+    rs.step(k, F);
   }
 };
 

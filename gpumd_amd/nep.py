@@ -348,6 +348,12 @@ class NEP:
         (default), or one record per trip on both lanes (option "angular_pair_trip"); bit-identical results"""
         self.set_option("angular_pair_trip", 1 if on else 0)
 
+    def set_fold_seam(self, on=True):
+        """single-domain NVE run loops in the scatter form: the fold of the window sums inside the integrator pass behind it
+        (default), or as a launch of its own (option "fold_seam"); bit-identical results (a window sum too large for the seam
+        sends a step back to the separate kernels without a list rebuild: include/nepmi.h)"""
+        self.set_option("fold_seam", 1 if on else 0)
+
     def describe(self):
         """the kernel forms the last force evaluation ran (counted rules of the engine, as text)"""
         import ctypes as C

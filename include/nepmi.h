@@ -507,6 +507,18 @@ int nepmi_engine_set_virial_mode(nepmi_engine* e, int mode);
  *       (tests/test_fused_pair_trip.py).  Shapes with at most four angular channels per lane (n_max_angular <= 6): with more, the
  *       trips' second set of (g, g') spills (carbon: 156 -> 168 B of scratch) and the one-record loops stay, as they do in the
  *       type-window and per-brick forms of the kernel.
+ *   "fold_seam": Single-domain NVE run loops whose force assembly takes the scatter form: value = 1 (default) -- the fold of the
+ *       window sums (one atom's entries of the up to eight brick windows that hold it) runs inside the integrator pass behind it
+ *       (second half-kick of the step, and on a step that neither records thermo data nor ends the call the first half-kick, drift,
+ *       wrap and skin check of the next), the force stays in registers and is stored only on record steps and the last step;
+ *       0: the fold and the integrator pass as two launches with the force written and read back in between.  The same
+ *       expressions on the same operands: bit-identical positions, velocities, forces, energies, virials and thermo rows
+ *       (tests/test_fold_seam.py).  A window sum large enough for a fold to reach the guard band of the fixed-point sums (fold_guard /
+ *       the most windows an atom lies in: 16 eV/A on whole bricks, 4.7 with a partly filled last brick) freezes the step in the
+ *       scatter kernel; its force evaluation is run again on the same lists with the separate kernels -- no list rebuild, so the
+ *       results stay bit-identical across it; only nepmi_engine_stats' discarded_steps counts the steps enqueued behind it -- and
+ *       the next 256 steps keep the separate kernels (describe: seam_vetoes=).  NEPMI_FOLD_SEAM=0 in the environment sets the
+ *       default of engines no caller reaches.
  *   "brick_force": ... and the scatter-form force assembly (find_force_radial, nep.cu:661-772; gpu_find_force_many_body, potential.cu:170-297) in
  *       the SAME kernel, one 512-thread workgroup per brick behind the radial pass: value = 1 where the fused angular kernel and the
  *       scatter form both apply, on shapes with two register-resident atom types, in single-domain engines; the partial forces and
