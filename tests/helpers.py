@@ -193,6 +193,116 @@ def oracle_thermo(volume, mass, pe, vel, virial):
     return th
 
 
+def _f32_fma(a, b, c):
+    """fmaf on float32 arrays: the product of two floats is exact in a double, the sum is rounded to double and then to float
+    (a second rounding that differs from fmaf's single one only on an exact halfway case of the double sum)"""
+    return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(np.float32)
+
+
+def oracle_skin_moved(h, pos_soa, pos_at_rebuild, pbc=(1, 1, 1)):
+    """The skin rule of nepo_run_nve (oracle/nep_oracle.c: "skin policy") restated in numpy: the float32 displacement of every
+    atom since the last rebuild, its minimum image (the float32 apply_mic of nep_oracle_core.inc, orthogonal and triclinic
+    branch), and a rebuild when any squared length exceeds 0.25 A^2 -> bool."""
+    n = pos_soa.size // 3
+    d = (np.asarray(pos_soa, dtype=np.float64) - np.asarray(pos_at_rebuild, dtype=np.float64)).astype(np.float32).reshape(3, n)
+    x, y, z = d[0].copy(), d[1].copy(), d[2].copy()
+    H = [float(v) for v in np.asarray(h, dtype=np.float64).reshape(-1)[:9]]
+    if all(H[k] == 0.0 for k in (1, 2, 3, 5, 6, 7)):
+        out = []
+        for c, k, on in ((x, 0, pbc[0]), (y, 4, pbc[1]), (z, 8, pbc[2])):
+            L = np.float32(H[k])
+            half = L * np.float32(0.5)
+            out.append(np.where(c < -half, c + L, np.where(c > half, c - L, c)) if on else c)
+        x, y, z = out
+    else:
+        # Box::get_inverse as nepo_invert_box forms it (cofactors over the determinant, in double), then rounded to float
+        inv = [H[4] * H[8] - H[5] * H[7], H[2] * H[7] - H[1] * H[8], H[1] * H[5] - H[2] * H[4],
+               H[5] * H[6] - H[3] * H[8], H[0] * H[8] - H[2] * H[6], H[2] * H[3] - H[0] * H[5],
+               H[3] * H[7] - H[4] * H[6], H[1] * H[6] - H[0] * H[7], H[0] * H[4] - H[1] * H[3]]
+        det = H[0] * (H[4] * H[8] - H[5] * H[7]) + H[1] * (H[5] * H[6] - H[3] * H[8]) + H[2] * (H[3] * H[7] - H[4] * H[6])
+        F = [np.float32(v) for v in H] + [np.float32(v / det) for v in inv]
+
+        def dot3(a, b, c, d_, e, f):  # fma(e, f, fma(c, d, a * b)) with scalars a, c, e
+            one = np.ones(n, dtype=np.float32)
+            return _f32_fma(e * one, f, _f32_fma(c * one, d_, a * b))
+        s = [dot3(F[9 + 3 * r], x, F[10 + 3 * r], y, F[11 + 3 * r], z) for r in range(3)]
+        s = [(c - np.rint(c)) if pbc[r] else c for r, c in enumerate(s)]
+        x, y, z = [dot3(F[3 * r], s[0], F[3 * r + 1], s[1], F[3 * r + 2], s[2]) for r in range(3)]
+    return bool(np.any((x * x + y * y + z * z).astype(np.float64) > 0.25))
+
+
+class OracleLoop:
+    """Run::perform_a_run composed from oracle pieces, one `Oracle.compute` per step, for `ensemble nve`, `nvt_ber`, `nvt_nhc`
+    and `nvt_bdp` (ensemble_ber.cu:195-235, ensemble_nhc.cu:166-232, ensemble_bdp.cu:71-104; the target ramp of
+    integrate.cu:341-344 with the step count of the CALL).  The state -- x, v, f, pe, w, the NHC chain array, the BDP generator
+    buffer, the positions of the last list rebuild -- is carried between calls of run(), like the engine's between two run calls.
+    `rebuilds` counts list rebuilds by the skin rule of nepo_run_nve, the initial build included."""
+
+    def __init__(self, orc, typ, h, x, vel, mass, dt, precision=32, bdp_seed=None, compute=None):
+        self.L = oracle_lib()
+        self.h, self.typ, self.mass, self.dt, self.n = h, typ, np.ascontiguousarray(mass, dtype=np.float64), float(dt), len(typ)
+        self.volume = abs(np.linalg.det(np.asarray(h, dtype=np.float64).reshape(-1)[:9].reshape(3, 3)))
+        self._compute = compute if compute is not None else (lambda xx: orc.compute(typ, h, xx, precision=precision, path=0))
+        self.x, self.v = np.array(x, dtype=np.float64), np.array(vel, dtype=np.float64)
+        self.pe, self.f, self.w = self._compute(self.x)  # Run: initial force before the loop
+        self.x_rebuild, self.rebuilds, self.rebuild_steps, self.steps_done = self.x.copy(), 1, [], 0
+        self.chain = None
+        self.rng = None
+        if bdp_seed is not None:
+            self.rng = C.create_string_buffer(self.L.nepo_bdp_sizeof())
+            self.L.nepo_bdp_seed(self.rng, bdp_seed)
+        self.factors = []  # every velocity scale factor the thermostat applied, in order
+
+    def _vv(self, first):
+        self.L.nepo_velocity_verlet(1 if first else 0, self.n, self.dt, _p(self.mass, _dp), _p(self.f, _dp), _p(self.x, _dp),
+                                    _p(self.v, _dp))
+
+    def thermo(self):
+        return oracle_thermo(self.volume, self.mass, self.pe, self.v, self.w)
+
+    def _nhc_half(self, target):
+        th = self.thermo()
+        s = self.L.nepo_nhc(_p(self.chain, _dp), th[0] * 3 * self.n * K_B, K_B * target, 3.0 * self.n, 0.5 * self.dt)
+        self.factors.append(s)
+        self.v *= s
+        return th
+
+    def run(self, ens, nsteps, t1=0.0, t2=0.0, tc=0.0, record_every=1):
+        """nsteps steps of `ens` in ("nve", "ber", "nhc", "bdp") -> (thermo rows [nsteps // record_every, 8] of the record
+        steps, list rebuilds so far)"""
+        assert ens in ("nve", "ber", "nhc", "bdp")
+        if ens == "nhc" and self.chain is None:  # a fresh chain per run; it continues across the calls of one run
+            self.chain = np.zeros(12)
+            self.L.nepo_nhc_init(self.n, t1, tc, self.dt, _p(self.chain, _dp))
+        rows = []
+        for step in range(nsteps):
+            target = t1 + (t2 - t1) * (step / nsteps)
+            if ens == "nhc":
+                self._nhc_half(target)
+            self._vv(True)
+            self.x = oracle_apply_pbc(self.h, self.x)
+            if oracle_skin_moved(self.h, self.x, self.x_rebuild):
+                self.x_rebuild = self.x.copy()
+                self.rebuilds += 1
+                self.rebuild_steps.append(self.steps_done + 1)
+            self.pe, self.f, self.w = self._compute(self.x)
+            self._vv(False)
+            if ens == "nhc":
+                th = self._nhc_half(target)
+            else:
+                th = self.thermo()
+                if ens == "ber":
+                    self.factors.append(np.sqrt(1.0 + (1.0 / tc) * (target / th[0] - 1.0)))
+                    self.v *= self.factors[-1]
+                elif ens == "bdp":
+                    self.factors.append(self.L.nepo_bdp_factor(self.rng, self.n, th[0], target, tc))
+                    self.v *= self.factors[-1]
+            self.steps_done += 1
+            if record_every > 0 and (step + 1) % record_every == 0:
+                rows.append(th)
+        return np.array(rows).reshape(-1, 8), self.rebuilds
+
+
 # --------------------------------------------------------------------------------------------
 # oracle/_ref: the reference's own NEP_CPU compiled in place
 # --------------------------------------------------------------------------------------------

@@ -414,21 +414,9 @@ def check_nvt_berendsen(drv, nsteps=30):
     vel = H.maxwell_velocities(mass, 300.0, seed=6)
     dt = 1.0 / H.TIME_UNIT
     t1, t2, tc = 300.0, 600.0, 20.0
-    vol = abs(np.linalg.det(np.asarray(h).reshape(3, 3)))
-    L = H.oracle_lib()
-    xo, vo = x.copy(), vel.copy()
-    pe, f, w = orc.compute(typ, h, xo, precision=32, path=0)
-    th_ref = []
-    for step in range(nsteps):
-        L.nepo_velocity_verlet(1, n, dt, H._p(mass, H._dp), H._p(f, H._dp), H._p(xo, H._dp), H._p(vo, H._dp))
-        xo = H.oracle_apply_pbc(h, xo)
-        pe, f, w = orc.compute(typ, h, xo, precision=32, path=0)
-        L.nepo_velocity_verlet(0, n, dt, H._p(mass, H._dp), H._p(f, H._dp), H._p(xo, H._dp), H._p(vo, H._dp))
-        th = H.oracle_thermo(vol, mass, pe, vo, w)
-        th_ref.append(th)
-        target = t1 + (t2 - t1) * (step / nsteps)
-        vo *= np.sqrt(1.0 + (1.0 / tc) * (target / th[0] - 1.0))
-    th_ref = np.array(th_ref)
+    loop = H.OracleLoop(orc, typ, h, x, vel, mass, dt)
+    th_ref, _ = loop.run("ber", nsteps, t1, t2, tc)
+    vo = loop.v
     eng = drv.engine(drv.model(nep), n)
     d_t, d_m, d_x, d_v = drv.dev(typ), drv.dev(mass), drv.dev(x), drv.dev(vel)
     d_pe, d_f, d_w = drv.zeros(n), drv.zeros(3 * n), drv.zeros(9 * n)
@@ -452,31 +440,9 @@ def check_nvt_nhc(drv, nsteps=30):
     dt = 1.0 / H.TIME_UNIT
     t1, t2, tc = 300.0, 500.0, 50.0
     vol = abs(np.linalg.det(np.asarray(h).reshape(3, 3)))
-    L = H.oracle_lib()
-    xo, vo = x.copy(), vel.copy()
-    pe, f, w = orc.compute(typ, h, xo, precision=32, path=0)
-    st = np.zeros(12)
-    L.nepo_nhc_init(n, t1, tc, dt, H._p(st, H._dp))
-    th_ref, fac = [], []
-
-    def half(target):
-        th = H.oracle_thermo(vol, mass, pe, vo, w)
-        s = L.nepo_nhc(H._p(st, H._dp), th[0] * 3 * n * H.K_B, H.K_B * target, 3.0 * n, 0.5 * dt)
-        fac.append(s)
-        return th, s
-
-    for step in range(nsteps):
-        target = t1 + (t2 - t1) * (step / nsteps)
-        _, s = half(target)
-        vo *= s
-        L.nepo_velocity_verlet(1, n, dt, H._p(mass, H._dp), H._p(f, H._dp), H._p(xo, H._dp), H._p(vo, H._dp))
-        xo = H.oracle_apply_pbc(h, xo)
-        pe, f, w = orc.compute(typ, h, xo, precision=32, path=0)
-        L.nepo_velocity_verlet(0, n, dt, H._p(mass, H._dp), H._p(f, H._dp), H._p(xo, H._dp), H._p(vo, H._dp))
-        th, s = half(target)
-        th_ref.append(th)
-        vo *= s
-    th_ref = np.array(th_ref)
+    loop = H.OracleLoop(orc, typ, h, x, vel, mass, dt)
+    th_ref, _ = loop.run("nhc", nsteps, t1, t2, tc)
+    vo, st, fac = loop.v, loop.chain, loop.factors
     assert min(fac) < 1.0 < max(fac) or max(abs(np.array(fac) - 1.0)) > 1e-6  # the chain really acts
 
     eng = drv.engine(drv.model(nep), n)
@@ -531,7 +497,6 @@ def check_nvt_bdp(drv, nsteps=30, seed=20240924):
     """`ensemble nvt_bdp 300 500 50` with a fixed seed: integrate_nvt_bdp_2 (ensemble_bdp.cu:71-104) against the
     same loop built from oracle pieces; the oracle restates MT19937 and libstdc++'s canonical-double draw, so the
     stochastic factors must agree draw for draw, not just statistically."""
-    import ctypes as C
     nep = H.golden("PbTe", "nep.txt")
     h, typ, x = H.pbte_supercell((2, 2, 2), rattle=0.01, seed=53)
     n = len(typ)
@@ -540,25 +505,9 @@ def check_nvt_bdp(drv, nsteps=30, seed=20240924):
     vel = H.maxwell_velocities(mass, 300.0, seed=8)
     dt = 1.0 / H.TIME_UNIT
     t1, t2, tc = 300.0, 500.0, 50.0
-    vol = abs(np.linalg.det(np.asarray(h).reshape(3, 3)))
-    L = H.oracle_lib()
-    rng = C.create_string_buffer(L.nepo_bdp_sizeof())
-    L.nepo_bdp_seed(rng, seed)
-    xo, vo = x.copy(), vel.copy()
-    pe, f, w = orc.compute(typ, h, xo, precision=32, path=0)
-    th_ref, fac = [], []
-    for step in range(nsteps):
-        target = t1 + (t2 - t1) * (step / nsteps)
-        L.nepo_velocity_verlet(1, n, dt, H._p(mass, H._dp), H._p(f, H._dp), H._p(xo, H._dp), H._p(vo, H._dp))
-        xo = H.oracle_apply_pbc(h, xo)
-        pe, f, w = orc.compute(typ, h, xo, precision=32, path=0)
-        L.nepo_velocity_verlet(0, n, dt, H._p(mass, H._dp), H._p(f, H._dp), H._p(xo, H._dp), H._p(vo, H._dp))
-        th = H.oracle_thermo(vol, mass, pe, vo, w)
-        th_ref.append(th)
-        s = L.nepo_bdp_factor(rng, n, th[0], target, tc)
-        fac.append(s)
-        vo *= s
-    th_ref, fac = np.array(th_ref), np.array(fac)
+    loop = H.OracleLoop(orc, typ, h, x, vel, mass, dt, bdp_seed=seed)
+    th_ref, _ = loop.run("bdp", nsteps, t1, t2, tc)
+    vo, fac = loop.v, np.array(loop.factors)
     assert np.abs(fac - 1.0).max() > 1e-4 and fac.min() < 1.0 < fac.max()  # noise of both signs
 
     eng = drv.engine(drv.model(nep), n)

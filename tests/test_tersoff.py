@@ -113,7 +113,7 @@ def test_oracle_vs_reference_kernels(case, tmp_path):
     np.testing.assert_allclose(v, v_o, rtol=1e-10, atol=1e-11)
 
 
-def _check_engine(drv, cells=(4, 4, 5), nve_steps=40):
+def _check_engine(drv, cells=(4, 4, 5), nve_steps=42, thermo_every=1):
     o = H.TersoffOracle(POT)
     h, typ, x = H.diamond(cells, 5.432, rattle=0.06, seed=3)
     n = len(typ)
@@ -128,16 +128,37 @@ def _check_engine(drv, cells=(4, 4, 5), nve_steps=40):
     np.testing.assert_allclose(v, v_o, rtol=1e-9, atol=1e-9)
     mx, nn, nl = H.engine_lists(drv, eng, n, 0, ld=int(nn_o.max()) + 2)
     H.assert_lists_equal(nn, nl, nn_o, nl_o)                    # local list bit-exact
-    # NVE: energy conservation (FP64 forces: tight) and a list rebuild on the way
+    # NVE: energy conservation (FP64 forces: tight) and a list rebuild on the way.  With thermo_every = 4 (the step count is no
+    # multiple of it) the force assembly of the steps between two records is deferred into the next step's first pass
+    # (TersoffSeamBody), and 2500 K puts the rebuilds on such steps: the replay of a frozen step crosses a deferred assembly
     mass = np.full(n, 28.085)
     vel = H.maxwell_velocities(mass, 2500.0, seed=4)
+    assert nve_steps % 4 != 0
+    loop = H.OracleLoop(None, typ, h, x, vel, mass, 1.0 / H.TIME_UNIT, compute=lambda xx: o.compute(typ, h, xx))
+    rows_o, rebuilds_o = loop.run("nve", nve_steps)
+    assert rebuilds_o - 1 >= 1 and all(s % 4 != 0 for s in loop.rebuild_steps), loop.rebuild_steps
     d_t, d_m, d_x, d_v = drv.dev(typ), drv.dev(mass), drv.dev(x), drv.dev(vel)
     d_pe, d_f, d_w = drv.zeros(n), drv.zeros(3 * n), drv.zeros(9 * n)
     eng = drv.engine(model, n)
     eng.force_compute(h, d_t, d_x, d_pe, d_f, d_w)
-    th = eng.run_nve(h, d_t, d_m, 1.0 / H.TIME_UNIT, nve_steps, d_x, d_v, d_pe, d_f, d_w, thermo_every=1)
-    etot = 1.5 * n * H.K_B * th[:, 0] + th[:, 1]
-    assert np.abs(etot - etot[0]).max() < 1e-3 * n  # O(dt^2) fluctuation at 2500 K, dt = 1 fs
+    th = eng.run_nve(h, d_t, d_m, 1.0 / H.TIME_UNIT, nve_steps, d_x, d_v, d_pe, d_f, d_w, thermo_every=thermo_every)
+    assert th.shape == (nve_steps // thermo_every, 8)
+    if thermo_every == 1:
+        etot = 1.5 * n * H.K_B * th[:, 0] + th[:, 1]
+        assert np.abs(etot - etot[0]).max() < 1e-3 * n  # O(dt^2) fluctuation at 2500 K, dt = 1 fs
+    # the recorded rows are the oracle loop's rows of those steps, and the final state its final state.  Everything is FP64 on
+    # both sides; the engine's forces agree with the oracle's to 1e-9 (above) and the trajectory is 25-42 steps long, so the
+    # tolerance of the final-force comparison below (1e-8) is kept for the rows, the velocities and the positions
+    rows_ref = rows_o[thermo_every - 1::thermo_every][:len(th)]
+    xs, vs = drv.host(d_x), drv.host(d_v)
+    st = eng.stats()
+    print("\n[tersoff %s thermo_every=%d] rebuilds engine %d oracle %d (initial one included; oracle's at steps %s), max deviation: "
+          "rows rel %.2e, positions %.2e A, velocities %.2e" % (drv.name, thermo_every, st.num_rebuild, rebuilds_o, loop.rebuild_steps,
+          np.abs(th / rows_ref - 1.0).max(), np.abs(xs - loop.x).max(), np.abs(vs - loop.v).max()))
+    np.testing.assert_allclose(th, rows_ref, rtol=1e-8, atol=1e-8)
+    np.testing.assert_allclose(xs, loop.x, rtol=0, atol=1e-8)
+    np.testing.assert_allclose(vs, loop.v, rtol=0, atol=1e-8)
+    assert st.num_rebuild == rebuilds_o, (st.num_rebuild, rebuilds_o)
     # final forces of the trajectory still equal the oracle on the final positions
     pe_o2, f_o2, _ = o.compute(typ, h, drv.host(d_x))
     np.testing.assert_allclose(drv.host(d_f), f_o2, rtol=1e-8, atol=1e-8)
@@ -152,6 +173,16 @@ def test_engine_logic_on_emulator():
 @pytest.mark.gpu
 def test_engine_on_gpu():
     _check_engine(H.GpuDriver())
+
+
+def test_deferred_assembly_against_the_oracle_loop_on_emulator():
+    """thermo_every = 4: the steps between two records defer their force assembly into the next step's first pass"""
+    _check_engine(H.EmuDriver(), cells=(3, 3, 4), nve_steps=25, thermo_every=4)
+
+
+@pytest.mark.gpu
+def test_deferred_assembly_against_the_oracle_loop_on_gpu():
+    _check_engine(H.GpuDriver(), thermo_every=4)
 
 
 @pytest.mark.gpu
