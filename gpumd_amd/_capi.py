@@ -90,6 +90,9 @@ SYMBOLS = {
     "nepmi_berendsen_scale": (C.c_int, [VP, c_i64, C.c_double, C.c_double, VP, VP]),
     "nepmi_run_nvt_ber": (C.c_int, [VP, c_dp, c_ip, c_i64, VP, VP, C.c_double, c_i64, C.c_double, C.c_double,
                                     C.c_double, VP, VP, VP, VP, VP, c_i64, c_dp]),
+    "nepmi_berendsen_pressure": (C.c_int, [VP, c_i64, C.c_int, c_dp, c_dp, VP, c_dp, VP]),
+    "nepmi_run_npt_ber": (C.c_int, [VP, c_dp, c_ip, c_i64, VP, VP, C.c_double, c_i64, C.c_double, C.c_double,
+                                    C.c_double, C.c_int, c_dp, c_dp, VP, VP, VP, VP, VP, c_i64, c_dp, c_dp]),
     "nepmi_nhc_init": (C.c_int, [VP, c_i64, C.c_double, C.c_double, C.c_double, VP]),
     "nepmi_nhc_half_step": (C.c_int, [VP, c_i64, C.c_double, C.c_double, VP, VP, VP]),
     "nepmi_run_nvt_nhc": (C.c_int, [VP, c_dp, c_ip, c_i64, VP, VP, C.c_double, c_i64, C.c_double, C.c_double,

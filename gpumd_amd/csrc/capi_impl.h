@@ -315,6 +315,79 @@ int nepmi_run_nvt_ber(
   });
 }
 
+// the refusals of Integrate::parse_ensemble for `npt_ber` (integrate.cu:649-692), with its messages
+static int npt_check(const double h[9], const int pbc[3], int num_p, const double* p_target, const double* p_coupling, nepmi::NptSpec& s)
+{
+  if (!h || !pbc || !p_target || !p_coupling)
+    return fail(NEPMI_ERR_ARG, "null argument");
+  if (num_p != 1 && num_p != 3 && num_p != 6)
+    return fail(NEPMI_ERR_ARG, "npt_ber: the number of target pressure components should be 1, 3 or 6");
+  const bool triclinic = h[1] != 0 || h[2] != 0 || h[3] != 0 || h[5] != 0 || h[6] != 0 || h[7] != 0;
+  const bool open_dir = pbc[0] == 0 || pbc[1] == 0 || pbc[2] == 0;
+  if (num_p == 3 && triclinic)
+    return fail(NEPMI_ERR_ARG, "Cannot use triclinic box with only 3 target pressure components.");
+  if (num_p == 1 && triclinic)
+    return fail(NEPMI_ERR_ARG, "Cannot use triclinic box with only 1 target pressure component.");
+  if (num_p == 1 && open_dir)
+    return fail(NEPMI_ERR_ARG, "Cannot use isotropic pressure with non-periodic boundary in any direction.");
+  if (num_p == 6 && open_dir)
+    return fail(NEPMI_ERR_ARG, "Cannot use 6 pressure components with non-periodic boundary in any direction.");
+  std::memset(&s, 0, sizeof(s));
+  s.num_p = num_p;
+  for (int k = 0; k < num_p; ++k) {
+    if (!(p_coupling[k] >= 0.0))
+      return fail(NEPMI_ERR_ARG, "npt_ber: pressure coupling should be >= 0");
+    s.p0[k] = p_target[k];
+    s.pc[k] = p_coupling[k];
+  }
+  return NEPMI_OK;
+}
+
+int nepmi_berendsen_pressure(
+  nepmi_engine* e, int64_t n, int num_p, const double p_target[6], const double p_coupling[6], const double* thermo8,
+  double h[9], double* pos)
+{
+  if (!e || !thermo8 || !pos)
+    return fail(NEPMI_ERR_ARG, "bad argument");
+  // open directions: those of the engine's last force evaluation (all periodic before the first)
+  int pbc[3] = {1, 1, 1};
+  if (e->e->num_compute > 0)
+    for (int d = 0; d < 3; ++d)
+      pbc[d] = e->e->box().pbc[d];
+  nepmi::NptSpec s;
+  const int st = npt_check(h, pbc, num_p, p_target, p_coupling, s);
+  if (st != NEPMI_OK)
+    return st;
+  return guarded([&] { e->e->berendsen_pressure(n, s, pbc, thermo8, h, pos); });
+}
+
+int nepmi_run_npt_ber(
+  nepmi_engine* e, double h[9], const int pbc[3], int64_t n, const int* type, const double* mass, double dt,
+  int64_t nsteps, double t1, double t2, double t_coup, int num_p, const double p_target[6], const double p_coupling[6],
+  double* pos, double* vel, double* pe, double* force, double* virial, int64_t thermo_every, double* thermo_host,
+  double* box_host)
+{
+  if (!e)
+    return fail(NEPMI_ERR_ARG, "null engine");
+  if (t_coup < 1.0)
+    return fail(NEPMI_ERR_ARG, "Temperature coupling should >= 1.");
+  nepmi::NptSpec s;
+  const int st = npt_check(h, pbc, num_p, p_target, p_coupling, s);
+  if (st != NEPMI_OK)
+    return st;
+  double h_out[9];
+  s.h_out = h_out;
+  s.box_host = box_host;
+  const int rc = guarded([&] {
+    e->e->run_md(e->e->kBer, h, pbc, n, type, mass, dt, nsteps, t1, t2, t_coup, pos, vel, pe, force, virial, thermo_every,
+                 thermo_host, &s);
+  });
+  if (rc == NEPMI_OK)
+    for (int k = 0; k < 9; ++k)
+      h[k] = h_out[k];
+  return rc;
+}
+
 int nepmi_nhc_init(nepmi_engine* e, int64_t n, double temperature, double t_coup, double dt, double* chain_state)
 {
   if (!e || !chain_state)
@@ -589,6 +662,8 @@ int nepmi_engine_set_option(nepmi_engine* e, const char* name, double value)
   }
   else if (n == "win_static")
     eng.set_win2(iv != 0);
+  else if (n == "keep_lists_on_box_change")
+    eng.set_keep_lists(iv != 0);
   else if (n == "stepwise_loops")
     eng.set_stepwise_loops(iv != 0);
   else if (n == "mfma")

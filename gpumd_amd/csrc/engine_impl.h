@@ -176,6 +176,56 @@ inline void box_from_h9(const double h9[9], const int pbc[3], BoxD& box)
   box.rfree2 = tmin < 1.0e29 ? (float)(0.49 * tmin * 0.49 * tmin) : 3.0e38f;
 }
 
+// Berendsen barostat of `ensemble npt_ber` (Ensemble_BER with type 11): what the run loop needs besides the thermostat's arguments
+struct NptSpec {
+  int num_p;        // 1 isotropic, 3 orthogonal, 6 triclinic (integrate.cu:631-693)
+  double p0[6];     // target pressures, natural units; Voigt xx yy zz yz xz xy for 6
+  double pc[6];     // pressure_coupling = 1 / (3 tau_p C), natural units, the same order
+  double* h_out;    // HOST, 9: the box after the last step
+  double* box_host; // HOST, 9 per thermo record: the box after that step's scaling; or nullptr
+};
+
+// cpu_pressure_isotropic / _orthogonal / _triclinic (ensemble_ber.cu:88-176, without the deform branches): the scale factors from
+// find_thermo's row (thermo8 on the HOST: T, U, sxx, syy, szz, sxy, sxz, syz) and the scaled box, the same expressions in the same
+// order.  mu is always filled as a 3x3 matrix; the one- and three-component forms use its diagonal only.
+inline void berendsen_box_factors(const NptSpec& s, const int pbc[3], const double* thermo8, double h[9], double mu[9])
+{
+  const double* p = thermo8 + 2;
+  for (int k = 0; k < 9; ++k)
+    mu[k] = 0.0;
+  if (s.num_p == 1) {
+    const double scale_factor = 1.0 - s.pc[0] * (s.p0[0] - (p[0] + p[1] + p[2]) * 0.3333333333333333);
+    h[0] *= scale_factor;
+    h[4] *= scale_factor;
+    h[8] *= scale_factor;
+    mu[0] = mu[4] = mu[8] = scale_factor;
+  } else if (s.num_p == 3) {
+    for (int d = 0; d < 3; ++d) {
+      const double scale_factor = pbc[d] ? 1.0 - s.pc[d] * (s.p0[d] - p[d]) : 1.0;
+      if (pbc[d])
+        h[4 * d] *= scale_factor;
+      mu[4 * d] = scale_factor;
+    }
+  } else {
+    mu[0] = 1.0 - s.pc[0] * (s.p0[0] - p[0]);    // xx
+    mu[4] = 1.0 - s.pc[1] * (s.p0[1] - p[1]);    // yy
+    mu[8] = 1.0 - s.pc[2] * (s.p0[2] - p[2]);    // zz
+    mu[3] = mu[1] = -s.pc[5] * (s.p0[5] - p[3]); // xy
+    mu[6] = mu[2] = -s.pc[4] * (s.p0[4] - p[4]); // xz
+    mu[7] = mu[5] = -s.pc[3] * (s.p0[3] - p[5]); // yz
+    double h_old[9];
+    for (int i = 0; i < 9; ++i)
+      h_old[i] = h[i];
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) {
+        double tmp = 0.0;
+        for (int k = 0; k < 3; ++k)
+          tmp += mu[r * 3 + k] * h_old[k * 3 + c];
+        h[r * 3 + c] = tmp;
+      }
+  }
+}
+
 template <class B>
 class EngineT
 {
@@ -220,6 +270,7 @@ public:
   const Bufs& bufs() const { return b_; }
   int64_t num_atoms() const { return N_; }
   int64_t num_compute = 0, num_rebuild = 0, num_discarded = 0;
+  int64_t num_remetric = 0; // box changes served by remetric() instead of a list rebuild
   int64_t num_range_handovers = 0; // times the scatter form was left for the gather form (guard band of its fixed-point sums)
   // kPhaseBoundaryRadial / kPhaseAfterRadial: kPhaseBoundary in two parts, so that the boundary bricks' radial pass can be
   // enqueued on the communication stream right behind the ghost unpack (force_kernels_on) and run beside the tail of the
@@ -296,14 +347,20 @@ public:
       return false;
     }
     last_small_ = false;
-    if (have_list_ && !same_box(box))
-      need_rebuild = true;
+    if (have_list_ && !same_box(box)) {
+      // keep_lists_on_box_change: a homogeneous deformation keeps the cells and the lists (remetric); the skin rule below, with
+      // x0s still in the old metric, sees the affine motion like the reference's x0/y0/z0 (neighbor.cu:646-684)
+      if (keep_lists_ && !need_rebuild && model_.kind == 0 && !external_skin_ && same_pbc(box))
+        remetric(box);
+      else
+        need_rebuild = true;
+    }
     box_ = box;
     if (!need_rebuild) {
       be_.memset(b_.flags + kFlagMoved, 0, sizeof(int));
       CheckGatherBody cg{box_, b_, pos, 0};
       be_.template launch<128>(kSlotGather, N_, cg);
-      if (!external_skin_) { // the one host round trip of a per-call force evaluation (neighbor.cu:752 does the same)
+      if (!external_skin_ && !skip_entry_skin_) { // the one host round trip of a per-call force evaluation (neighbor.cu:752 does the same)
         int flags[kNumFlags];
         be_.d2h(flags, b_.flags, sizeof(flags));
         check_overflow(flags);
@@ -390,11 +447,31 @@ public:
     for (int k = 0; k < 9; ++k)
       if (box.h[k] != box_.h[k])
         return false;
+    return same_pbc(box);
+  }
+  bool same_pbc(const BoxD& box) const
+  {
     for (int d = 0; d < 3; ++d)
       if (box.pbc[d] != box_.pbc[d])
         return false;
     return true;
   }
+
+  // A homogeneous deformation of the box between two list rebuilds: everything the rebuild derived from h is recomputed for the
+  // new box (host arithmetic only) -- the fixed-point frame of the window kernels, the cell edge vectors in grid units, the
+  // retake band.  What stays: the cells (their FRACTIONAL widths wg.cell_frac, nbx/nby/nbz, the bricks), every atom's cell
+  // (kcell), wtab / wcode, the Verlet lists, the fold map and the halo rows -- all integers that a strain does not change -- and
+  // x0s, on purpose in the OLD metric: the skin rule then counts the affine motion.  Every kernel receives BoxD and Bufs by value
+  // at its launch, so nothing on the device caches h; every prec must be rewritten (make_prec with the new box) before a window
+  // kernel runs: CheckGatherBody on the per-call path, ResidentBarostatBody in the NPT run loop.  Bufs::rc_inv_cell is read by the
+  // rebuild's binning only, which sets it.  Callers check: a valid list, NEP, same n and pbc, neither box small.
+  void remetric(const BoxD& box)
+  {
+    box_ = box;
+    set_metric(true);
+    ++num_remetric;
+  }
+  void set_keep_lists(bool on) { keep_lists_ = on; }
 
   void apply_pbc(const double h9[9], const int pbc[3], int64_t n, double* pos)
   {
@@ -449,6 +526,21 @@ public:
       BerendsenBody body{n, temperature, coupling, thermo8, vel};
       be_.template launch<256>(kSlotMisc, n, body);
     }
+  }
+
+  // The barostat half of Ensemble_BER::compute2 (type 11) for a host that steps by hand: factors from thermo8 (DEVICE, one look),
+  // h (HOST) scaled in place, pos (DEVICE, caller order) scaled; no wrap
+  void berendsen_pressure(int64_t n, const NptSpec& spec, const int pbc[3], const double* thermo8, double h[9], double* pos)
+  {
+    double th[8];
+    be_.d2h(th, thermo8, sizeof(th)); // (waits for the stream: find_thermo has finished)
+    ScalePositionsBody body;
+    std::memset(&body, 0, sizeof(body));
+    berendsen_box_factors(spec, pbc, th, h, body.mu);
+    body.N = n;
+    body.full = spec.num_p == 6 ? 1 : 0;
+    body.pos = pos;
+    be_.template launch<256>(kSlotMisc, n, body);
   }
 
   // Ensemble_NHC (ensemble_nhc.cu): chain state in caller-owned device memory (kNhcStateSize doubles)
@@ -626,12 +718,18 @@ public:
   void run_md(
     int ens, const double h9[9], const int pbc[3], int64_t n, const int* type, const double* mass, double dt,
     int64_t nsteps, double t1, double t2, double tcoup, double* pos, double* vel, double* pe, double* force,
-    double* virial, int64_t thermo_every, double* thermo_host)
+    double* virial, int64_t thermo_every, double* thermo_host, const NptSpec* npt = nullptr)
   {
     BoxD box;
     box_from_h9(h9, pbc, box);
     if (n < 1 || n > cap_)
       throw EngineError{-4, "number of atoms exceeds the engine's capacity"};
+    if (npt) {
+      if (model_.kind != 0)
+        throw EngineError{-4, "npt_ber is implemented for NEP models only (Tersoff-1989: not supported)"};
+      for (int k = 0; k < 9; ++k)
+        npt->h_out[k] = h9[k];
+    }
     struct LoopCtx { // the steps of this loop need forces, energies and the total virial only
       EngineT& e;
       bool was;
@@ -642,13 +740,22 @@ public:
       // (set_stepwise_loops: the Langevin ensembles as the plain sequence of the per-call entry points on the caller's
       // arrays -- what the resident forms are checked against, bit for bit)
       run_md_small_box(ens, h9, pbc, n, type, mass, dt, nsteps, t1, t2, tcoup, pos, vel, pe, force, virial, thermo_every,
-                       thermo_host);
+                       thermo_host, npt);
       return;
     }
     if (nsteps <= 0)
       return;
     // entry: lists valid for the caller's positions, state imported
-    prepare_lists(h9, pbc, n, type, pos, nullptr);
+    // (NPT: the positions a previous call scaled have not been through a skin check yet, and the reference asks the rule only
+    // after the next first half-step -- so does the loop: the entry check would count a rebuild the reference never makes)
+    skip_entry_skin_ = npt != nullptr;
+    try {
+      prepare_lists(h9, pbc, n, type, pos, nullptr);
+    } catch (...) {
+      skip_entry_skin_ = false;
+      throw;
+    }
+    skip_entry_skin_ = false;
     resident_alloc();
     resident_import(vel, mass, pe, force, virial);
     if (ens == kNhc) {
@@ -678,7 +785,7 @@ public:
     auto tag_of = [](int64_t step) { return (int)(step % 1000000000) + 1; };
     auto target_of = [&](int64_t step) { return t1 + (t2 - t1) * ((double)step / (double)nsteps); };
     auto thermo_now = [&]() {
-      be_.thermo(kSlotThermo, N_, box.volume, b_.mi, b_.fo, b_.vi, b_.fo + (int64_t)kOutW * N_, thermo_dev_, thermo_scratch_);
+      be_.thermo(kSlotThermo, N_, box_.volume, b_.mi, b_.fo, b_.vi, b_.fo + (int64_t)kOutW * N_, thermo_dev_, thermo_scratch_); // (box_: the current box of an NPT loop)
     };
     auto nhc_half = [&](double target) { // one thermostat half-step on the internal velocities
       thermo_now();
@@ -777,7 +884,7 @@ public:
         set_temperature(t1 + (t2 - t1) * ((double)(step + 2) / (double)nsteps));
       const bool record = thermo_every > 0 && (step + 1) % thermo_every == 0;
       const bool last = step + 1 == nsteps;
-      step_outputs_ = record || last; // per-atom energies and virials: read at thermo records and at the exit only
+      step_outputs_ = record || last || npt != nullptr; // per-atom energies and virials: read at thermo records and at the exit only (NPT: the barostat reads the stresses of every step)
       b_.trip_tag = tag_of(step);     // (scatter form: a force beyond its fixed-point guard band freezes the loop at this step)
       tersoff_defer_ = NEPMI_TERSOFF_SEAM && model_.kind == 1 && ens == kNve && !record && !last;
       // scatter form: the fold rides in the next pass over the atoms -- the first pass of the next step, or on a record / last step
@@ -806,7 +913,10 @@ public:
           fold_seam(ResidentStepBody{box_, b_, dt, 1, 0, 0}, true);
         else
           be_.template launch<256>(kSlotVV, N_, ResidentStepBody{box_, b_, dt, 1, 0, 0});
-        if (ens == kBer) {
+        if (ens == kBer && npt) {
+          thermo_now();
+          need_sync = true; // the box factors are formed on the host from this row, as in the reference (cpu_pressure_*)
+        } else if (ens == kBer) {
           thermo_now();
           if (1.0 / tcoup > 1.0e-5) { // ensemble_ber.cu:223
             be_.template launch<64>(kSlotMisc, 1, BerendsenFactorBody{b_.flags, target, 1.0 / tcoup, thermo_dev_, factor_dev_});
@@ -835,6 +945,37 @@ public:
             double T = 0.0;
             be_.d2h(&T, thermo_dev_, sizeof(double));
             be_.template launch<256>(kSlotVV, N_, ResidentScaleBody{b_, nullptr, bdp_factor(N_, T, target, tcoup)});
+          }
+          if (npt) {
+            // Ensemble_BER::compute2 with type 11 on a step that stands: factors on the host, the engine re-metricked for the
+            // scaled box (cells and lists stay), then ONE pass: v *= factor_T, x <- mu x, posq / prec in the new metric
+            double th[8];
+            be_.d2h(th, thermo_dev_, sizeof(th));
+            ResidentBarostatBody bb;
+            std::memset(&bb, 0, sizeof(bb));
+            double hn[9];
+            for (int k = 0; k < 9; ++k)
+              hn[k] = box_.h[k];
+            berendsen_box_factors(*npt, pbc, th, hn, bb.mu);
+            const double coupling = 1.0 / tcoup;
+            bb.scale_v = coupling > 1.0e-5 ? 1 : 0; // ensemble_ber.cu:223
+            bb.factor_t = bb.scale_v ? std::sqrt(1.0 + coupling * (target / th[0] - 1.0)) : 1.0;
+            bb.full = npt->num_p == 6 ? 1 : 0;
+            BoxD nbox;
+            box_from_h9(hn, pbc, nbox);
+            if (!(nbox.volume > 0.0) || is_small_box(nbox))
+              throw EngineError{-7, "npt_ber: the barostat has shrunk the box to a periodic thickness <= 2.5 (rc + skin) (or the box has "
+                                    "collapsed): the small-box branch cannot take over inside a run call"};
+            if (last && virial)
+              exact_virials(); // per-atom virials leave the engine: on the positions and the box they were evaluated with, before the scaling
+            remetric(nbox);
+            bb.box = box_;
+            bb.b = b_;
+            be_.template launch<256>(kSlotVV, N_, bb);
+            for (int k = 0; k < 9; ++k)
+              npt->h_out[k] = hn[k];
+            if (record && npt->box_host && thermo_rows)
+              std::memcpy(npt->box_host + 9 * ((step + 1) / thermo_every - 1), hn, sizeof(hn));
           }
         }
       } else if ((step + 1) % (poll_fixed ? poll_fixed : (step - calm_since >= kPollCalmSteps ? kPollEveryCalm : kPollEvery)) == 0) {
@@ -914,10 +1055,13 @@ public:
   void run_md_small_box(
     int ens, const double h9[9], const int pbc[3], int64_t n, const int* type, const double* mass, double dt,
     int64_t nsteps, double t1, double t2, double tcoup, double* pos, double* vel, double* pe, double* force,
-    double* virial, int64_t thermo_every, double* thermo_host)
+    double* virial, int64_t thermo_every, double* thermo_host, const NptSpec* npt = nullptr)
   {
     BoxD box;
     box_from_h9(h9, pbc, box);
+    double hcur[9]; // the box of the step (NPT: scaled at the end of every step)
+    for (int k = 0; k < 9; ++k)
+      hcur[k] = h9[k];
     if (ens == kNhc) {
       if (!nhc_dev_)
         nhc_dev_ = dalloc<double>(kNhcStateSize);
@@ -941,14 +1085,14 @@ public:
         half_drift(n, dt, pos, vel);
         bao_o_step(n, t1, tcoup, mass, vel);
         half_drift(n, dt, pos, vel);
-        apply_pbc(h9, pbc, n, pos); // Force::compute wraps (force.cu:787-795)
+        apply_pbc(hcur, pbc, n, pos); // Force::compute wraps (force.cu:787-795)
       } else {
         velocity_verlet(true, n, dt, mass, force, pos, vel, &box);
       }
       zero_properties(n, pe, force, virial);
       if (model_.temperature_model && ens != kNve) // as in run_md
         set_temperature(t1 + (t2 - t1) * ((double)(step + 2) / (double)nsteps));
-      potential_compute(h9, pbc, n, type, pos, pe, force, virial);
+      potential_compute(hcur, pbc, n, type, pos, pe, force, virial);
       velocity_verlet(false, n, dt, mass, force, pos, vel, nullptr);
       const bool record = thermo_every > 0 && (step + 1) % thermo_every == 0;
       if (ens == kLan) // Ensemble_LAN::compute2 (:241-262): second half-step of the thermostat, then find_thermo
@@ -961,7 +1105,15 @@ public:
         nhc_half_step(n, target, dt, thermo_dev_, nhc_dev_, vel);
       else if (ens == kBdp)
         bdp_scale(n, target, tcoup, thermo_dev_, vel);
-      if (record) {
+      if (npt) { // (after the thermostat, from the same row: ensemble_ber.cu:235-284)
+        berendsen_pressure(n, *npt, pbc, thermo_dev_, hcur, pos);
+        box_from_h9(hcur, pbc, box);
+        for (int k = 0; k < 9; ++k)
+          npt->h_out[k] = hcur[k];
+        if (record && npt->box_host && thermo_host)
+          std::memcpy(npt->box_host + 9 * rec, hcur, sizeof(hcur));
+      }
+      if (record && thermo_host) {
         be_.d2h(thermo_host + 8 * rec, thermo_dev_, 8 * sizeof(double));
         ++rec;
       }
@@ -1342,6 +1494,41 @@ private:
     NEPMI_SHAPE_DISPATCH(small_force_kernels_shape, 1, ())
   }
 
+  // What the window kernels derive from h, for box_ and the cell grid in Bufs; keep_cells: the cells' fractional widths stay
+  // (remetric), else they follow from the cell edge the rebuild has just chosen
+  void set_metric(bool keep_cells)
+  {
+    const int nb[3] = {b_.nbx, b_.nby, b_.nbz};
+    // fixed-point frame of the window kernels: +-R covers the 8x8x8-cell window seen from its centre (the widened
+    // edge cells of an open direction and half a cell of outliers included) plus the drift between two rebuilds
+    double R = 0.0, lmax = 0.0;
+    for (int c = 0; c < 3; ++c) {
+      double r = 0.0;
+      for (int d = 0; d < 3; ++d)
+        r += 6.5 * std::fabs(box_.h[3 * c + d]) / nb[d];
+      R = r > R ? r : R;
+    }
+    R += 2.0;
+    WinGeom& g = b_.wg;
+    g.inv_unit = 1073741824.0 / R;
+    g.unit = (float)(R / 1073741824.0);
+    g.unit2 = g.unit * g.unit;
+    for (int d = 0; d < 3; ++d) {
+      const double len = std::sqrt(box_.h[d] * box_.h[d] + box_.h[3 + d] * box_.h[3 + d] + box_.h[6 + d] * box_.h[6 + d]);
+      if (box_.pbc[d] && len > lmax)
+        lmax = len;
+      if (!keep_cells)
+        g.cell_frac[d] = 1.0 / (box_.thickness[d] * b_.rc_inv_cell);
+      for (int c = 0; c < 3; ++c) {
+        g.cv[3 * c + d] = (int)std::llround(box_.h[3 * c + d] * g.cell_frac[d] * g.inv_unit);
+        g.sv[3 * c + d] = (int)std::llround(box_.h[3 * c + d] * (1.0 - nb[d] * g.cell_frac[d]) * g.inv_unit);
+      }
+    }
+    // The reference forms r12 in FP32 with an FP32 minimum image: across a periodic face that carries rounding of
+    // the order of ulp(box length).  A list decision closer to a cutoff than this band is retaken exactly.
+    g.band = (float)(1.0e-4 + 4.0 * model_.rc_radial_max * lmax * 1.2e-7);
+  }
+
   // Neighbor::find_neighbor (neighbor.cu:303-365) + find_cell_list (:164-215)
   void rebuild(const int* type, const double* pos)
   {
@@ -1444,35 +1631,7 @@ private:
       bin_grid();
       ncell = set_grid();
     }
-    {
-      // fixed-point frame of the window kernels: +-R covers the 8x8x8-cell window seen from its centre (the widened
-      // edge cells of an open direction and half a cell of outliers included) plus the drift between two rebuilds
-      double R = 0.0, lmax = 0.0;
-      for (int c = 0; c < 3; ++c) {
-        double r = 0.0;
-        for (int d = 0; d < 3; ++d)
-          r += 6.5 * std::fabs(box_.h[3 * c + d]) / nb[d];
-        R = r > R ? r : R;
-      }
-      R += 2.0;
-      WinGeom& g = b_.wg;
-      g.inv_unit = 1073741824.0 / R;
-      g.unit = (float)(R / 1073741824.0);
-      g.unit2 = g.unit * g.unit;
-      for (int d = 0; d < 3; ++d) {
-        const double len = std::sqrt(box_.h[d] * box_.h[d] + box_.h[3 + d] * box_.h[3 + d] + box_.h[6 + d] * box_.h[6 + d]);
-        if (box_.pbc[d] && len > lmax)
-          lmax = len;
-        g.cell_frac[d] = 1.0 / (box_.thickness[d] * b_.rc_inv_cell);
-        for (int c = 0; c < 3; ++c) {
-          g.cv[3 * c + d] = (int)std::llround(box_.h[3 * c + d] * g.cell_frac[d] * g.inv_unit);
-          g.sv[3 * c + d] = (int)std::llround(box_.h[3 * c + d] * (1.0 - nb[d] * g.cell_frac[d]) * g.inv_unit);
-        }
-      }
-      // The reference forms r12 in FP32 with an FP32 minimum image: across a periodic face that carries rounding of
-      // the order of ulp(box length).  A list decision closer to a cutoff than this band is retaken exactly.
-      g.band = (float)(1.0e-4 + 4.0 * model_.rc_radial_max * lmax * 1.2e-7);
-    }
+    set_metric(false);
     be_.memset(b_.cell_count, 0, sizeof(int) * (ncell + 1));
     be_.memset(b_.cell_fill, 0, sizeof(int) * ncell);
     be_.memset(b_.cell_ghost, 0, sizeof(int) * ncell);
@@ -2610,6 +2769,9 @@ private:
   int win_lanes_ = 0;
   int win_max_atoms_ = 0; // set_win_max_atoms (0: the rule)
   bool external_skin_ = false;
+  // "keep_lists_on_box_change"; NEPMI_KEEP_LISTS=1 in the environment sets the default (a drop-in host that cannot reach the option)
+  bool keep_lists_ = std::getenv("NEPMI_KEEP_LISTS") && std::atoi(std::getenv("NEPMI_KEEP_LISTS")) != 0;
+  bool skip_entry_skin_ = false; // run_md of an NPT loop: the skin rule is first asked after the first step's drift, as in the reference
 #ifndef NEPMI_BRICK_FILL
 #define NEPMI_BRICK_FILL 256 // A/B switch (profiles/ab_variants.sh); r3l: 253 -> 256 lets PbTe 1 M atoms take the 64^3 grid (4,096 full bricks
                              // instead of 4,913 of which 817 partly filled): force assembly 0.524 -> 0.490 ms, step 1.650 -> 1.596; 264 and 280 pick the same grid

@@ -299,4 +299,66 @@ struct BerendsenFactorBody {
   }
 };
 
+// Berendsen barostat step of the NPT run loop (Ensemble_BER::compute2 with type 11, ensemble_ber.cu:223-284) as ONE pass over the
+// owned atoms in internal order: the thermostat's velocity factor (gpu_berendsen_temperature), the position scaling x <- mu x
+// (gpu_pressure_isotropic / _orthogonal / _triclinic, npt_utilities.cuh) and the fixed-point record of the scaled position in the
+// NEW metric (the host has re-metricked the engine: `box` and b.wg are the new ones; cells, lists and pad stay).  No wrap: like the
+// reference, the next step's first pass wraps.  Unwrapped positions are not scaled (the reference scales position_per_atom only).
+struct ResidentBarostatBody {
+  BoxD box; // the box AFTER the scaling
+  Bufs b;
+  double factor_t; // velocity factor, computed on the host from the same thermo row
+  int scale_v;     // 0: 1 / T_coup <= 1e-5, the thermostat is skipped (ensemble_ber.cu:223)
+  int full;        // 1: six-component form, x <- mu x with the full matrix; 0: per-component products with mu[0], mu[4], mu[8]
+  double mu[9];
+  NEPMI_HD void operator()(int64_t k) const
+  {
+#pragma clang fp contract(off)
+    if (b.flags[kFlagMoved] != 0 || b.lvl[k] < 2)
+      return;
+    const int64_t N = b.N;
+    if (scale_v) {
+      b.vi[k] *= factor_t;
+      b.vi[N + k] *= factor_t;
+      b.vi[2 * N + k] *= factor_t;
+    }
+    PosQ p = b.posq[k];
+    if (full) {
+      const double x = p.x, y = p.y, z = p.z;
+      p.x = mu[0] * x + mu[1] * y + mu[2] * z;
+      p.y = mu[3] * x + mu[4] * y + mu[5] * z;
+      p.z = mu[6] * x + mu[7] * y + mu[8] * z;
+    } else {
+      p.x *= mu[0];
+      p.y *= mu[4];
+      p.z *= mu[8];
+    }
+    b.posq[k] = p;
+    if (b.prec)
+      b.prec[k] = make_prec(box, b, k, p);
+  }
+};
+
+// the same scaling on a caller-order position array (nepmi_berendsen_pressure, the stepwise loop of small boxes)
+struct ScalePositionsBody {
+  int64_t N;
+  int full;
+  double mu[9];
+  double* pos;
+  NEPMI_HD void operator()(int64_t i) const
+  {
+#pragma clang fp contract(off)
+    const double x = pos[i], y = pos[N + i], z = pos[2 * N + i];
+    if (full) {
+      pos[i] = mu[0] * x + mu[1] * y + mu[2] * z;
+      pos[N + i] = mu[3] * x + mu[4] * y + mu[5] * z;
+      pos[2 * N + i] = mu[6] * x + mu[7] * y + mu[8] * z;
+    } else {
+      pos[i] = x * mu[0];
+      pos[N + i] = y * mu[4];
+      pos[2 * N + i] = z * mu[8];
+    }
+  }
+};
+
 } // namespace nepmi

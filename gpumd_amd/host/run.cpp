@@ -199,8 +199,74 @@ void Run::parse_one_keyword(const std::vector<std::string>& p)
                   "    final temperature is %g K.\n    tau_T is %g time_step.\n",
                   p[1] == "nvt_ber" ? "Berendsen" : p[1] == "nvt_nhc" ? "Nose-Hoover chain" : p[1] == "nvt_lan" ? "Langevin" : p[1] == "nvt_bao" ? "BAOAB Langevin" : "Bussi-Donadio-Parrinello",
                   temperature1, temperature2, temperature_coupling);
+    } else if (p[1] == "npt_ber") { // Integrate::parse_ensemble, integrate.cu:438-440, :569-603, :631-715, :1107-1154
+      if (p.size() != 8 && p.size() != 12 && p.size() != 18)
+        input_error("ensemble npt_ber should have 6, 10, or 16 parameters.");
+      auto real = [&](const std::string& s, double& out) {
+        char* end = nullptr;
+        out = std::strtod(s.c_str(), &end);
+        return end != s.c_str() && *end == '\0';
+      };
+      if (!real(p[2], temperature1))
+        input_error("Initial temperature should be a number.");
+      if (temperature1 <= 0.0)
+        input_error("Initial temperature should > 0.");
+      if (!real(p[3], temperature2))
+        input_error("Final temperature should be a number.");
+      if (temperature2 <= 0.0)
+        input_error("Final temperature should > 0.");
+      if (!real(p[4], temperature_coupling))
+        input_error("Temperature coupling should be a number.");
+      if (temperature_coupling < 1.0)
+        input_error("Temperature coupling should >= 1. \n(We have changed the convention for this input starting from GPUMD-V3.0; See the manual for details.)");
+      const int np = p.size() == 8 ? 1 : p.size() == 12 ? 3 : 6;
+      double elastic_modulus[6] = {0, 0, 0, 0, 0, 0}, tau_p = 0.0;
+      for (int i = 0; i < np; ++i)
+        if (!real(p[5 + i], target_pressure[i]))
+          input_error("Pressure should be a number.");
+      for (int i = 0; i < np; ++i) {
+        if (!real(p[5 + np + i], elastic_modulus[i]))
+          input_error("elastic modulus should be a number.");
+        if (elastic_modulus[i] <= 0)
+          input_error("elastic modulus should > 0.");
+      }
+      const double* h = box.cpu_h;
+      const bool triclinic = h[1] != 0 || h[2] != 0 || h[3] != 0 || h[5] != 0 || h[6] != 0 || h[7] != 0;
+      const bool open_dir = box.pbc_x == 0 || box.pbc_y == 0 || box.pbc_z == 0;
+      if (np == 3 && triclinic)
+        input_error("Cannot use triclinic box with only 3 target pressure components.");
+      if (np == 1 && triclinic)
+        input_error("Cannot use triclinic box with only 1 target pressure component.");
+      if (np == 1 && open_dir)
+        input_error("Cannot use isotropic pressure with non-periodic boundary in any direction.");
+      if (np == 6 && open_dir)
+        input_error("Cannot use 6 pressure components with non-periodic boundary in any direction.");
+      if (!real(p[2 * np + 5], tau_p))
+        input_error("Pressure coupling should be a number.");
+      if (tau_p < 1)
+        input_error("Pressure coupling should >= 1. \n(We have changed the convention for this input starting from GPUMD-V3.0; See the manual for details.)");
+      if (par_.world > 1)
+        input_error("ensemble npt_ber is not available in multi-GPU runs.");
+      num_target_pressure_components = np;
+      std::printf("Use NPT ensemble for this run.\n    choose the Berendsen method.\n    initial temperature is %g K.\n"
+                  "    final temperature is %g K.\n    tau_T is %g time_step.\n",
+                  temperature1, temperature2, temperature_coupling);
+      static const char* names[3][6] = {{"isotropic pressure", "", "", "", "", ""}, {"pressure_xx", "pressure_yy", "pressure_zz", "", "", ""},
+                                        {"pressure_xx", "pressure_yy", "pressure_zz", "pressure_yz", "pressure_xz", "pressure_xy"}};
+      for (int i = 0; i < np; ++i)
+        std::printf("    %s is %g GPa, modulus %g GPa.\n", names[np == 1 ? 0 : np == 3 ? 1 : 2][i], target_pressure[i], elastic_modulus[i]);
+      std::printf("    tau_p is %g time_step.\n", tau_p);
+      for (int i = 0; i < 6; ++i) { // integrate.cu:709-714, then GPa -> natural units, :1151-1154
+        pressure_coupling[i] = i < np ? 1.0 / (tau_p * 3.0 * elastic_modulus[i]) : 0.0;
+        if (elastic_modulus[i] > 2.0e3)
+          pressure_coupling[i] = 0.0;
+        target_pressure[i] /= PRESSURE_UNIT_CONVERSION;
+        pressure_coupling[i] *= PRESSURE_UNIT_CONVERSION;
+      }
+    } else if (p[1] == "npt_scr" || p[1] == "npt_mttk" || p[1] == "npt_nhc") {
+      input_error("ensemble " + p[1] + " is not available in gpumd-mi: npt_ber is the one constant-pressure ensemble (DESIGN.md section 8).");
     } else {
-      input_error("ensemble " + p[1] + " is not available in gpumd-mi yet (nve, nvt_ber, nvt_nhc, nvt_bdp, nvt_lan, nvt_bao; DESIGN.md section 8).");
+      input_error("ensemble " + p[1] + " is not available in gpumd-mi yet (nve, nvt_ber, nvt_nhc, nvt_bdp, nvt_lan, nvt_bao, npt_ber; DESIGN.md section 8).");
     }
     ensemble = p[1];
   } else if (k == "time_step") {
@@ -794,9 +860,13 @@ void Run::run_segment(int steps, double t_a, double t_b)
         die_on(nepmi_lan_half_step(e, N, target, temperature_coupling, atom.mass.data(), atom.velocity_per_atom.data()), "lan");
       if (ensemble != "nve" || s + 1 == steps)
         find_thermo();
-      if (ensemble == "nvt_ber")
+      if (ensemble == "nvt_ber" || ensemble == "npt_ber")
         die_on(nepmi_berendsen_scale(e, N, target, 1.0 / temperature_coupling, thermo.data(), atom.velocity_per_atom.data()), "ber");
-      else if (ensemble == "nvt_bdp")
+      if (ensemble == "npt_ber") { // Ensemble_BER::compute2 with type 11: from the same thermo row (ensemble_ber.cu:235-284)
+        die_on(nepmi_berendsen_pressure(e, N, num_target_pressure_components, target_pressure, pressure_coupling, thermo.data(),
+                                        box.cpu_h, atom.position_per_atom.data()), "ber pressure");
+        box.get_inverse();
+      } else if (ensemble == "nvt_bdp")
         die_on(nepmi_bdp_scale(e, N, target, temperature_coupling, thermo.data(), atom.velocity_per_atom.data()), "bdp");
       else if (ensemble == "nvt_nhc")
         die_on(nepmi_nhc_half_step(e, N, target, time_step, thermo.data(), nhc_state_, atom.velocity_per_atom.data()), "nhc");
@@ -812,7 +882,12 @@ void Run::run_segment(int steps, double t_a, double t_b)
   else if (ensemble == "nvt_ber")
     st = nepmi_run_nvt_ber(e, box.cpu_h, pbc, N, atom.type.data(), atom.mass.data(), time_step, steps, t_a, t_b,
                            temperature_coupling, x, v, pe, f, w, steps, th);
-  else if (ensemble == "nvt_nhc")
+  else if (ensemble == "npt_ber") {
+    st = nepmi_run_npt_ber(e, box.cpu_h, pbc, N, atom.type.data(), atom.mass.data(), time_step, steps, t_a, t_b,
+                           temperature_coupling, num_target_pressure_components, target_pressure, pressure_coupling, x, v, pe, f,
+                           w, steps, th, nullptr);
+    box.get_inverse(); // box.cpu_h[0..8] is the box of the step now: thermo.out, dump_xyz and restart.xyz read it
+  } else if (ensemble == "nvt_nhc")
     st = nepmi_run_nvt_nhc(e, box.cpu_h, pbc, N, atom.type.data(), atom.mass.data(), time_step, steps, t_a, t_b,
                            temperature_coupling, x, v, pe, f, w, steps, th);
   else if (ensemble == "nvt_lan")
@@ -1066,6 +1141,8 @@ void Run::perform_a_run_dist()
     input_error("No potential is defined before run.");
   if (!dist_ready_)
     dist_setup_atoms();
+  if (ensemble == "npt_ber")
+    input_error("ensemble npt_ber is not available in multi-GPU runs.");
   if (observer.active)
     input_error("dump_observer is not available in multi-GPU runs.");
   if (active_.active)

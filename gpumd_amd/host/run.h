@@ -91,6 +91,9 @@ private:
   bool gpu_allocated = false;
   std::string ensemble = "nve";
   double temperature1 = 300.0, temperature2 = 300.0, temperature_coupling = 100.0; // nvt_ber, nvt_nhc
+  // npt_ber (Integrate::parse_ensemble, integrate.cu:631-715): natural units after parsing, Voigt order xx yy zz yz xz xy for 6
+  int num_target_pressure_components = 0;
+  double target_pressure[6] = {0, 0, 0, 0, 0, 0}, pressure_coupling[6] = {0, 0, 0, 0, 0, 0};
   double time_step = 1.0 / TIME_UNIT_CONVERSION;
   double global_time = 0.0;
   int number_of_steps = 0;

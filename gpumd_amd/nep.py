@@ -199,6 +199,54 @@ class NEP:
             self._ptr(force), self._ptr(virial), int(thermo_every), th.ctypes.data_as(_capi.c_dp)))
         return th[:nrec]
 
+    @staticmethod
+    def _pressure6(p_target, p_coupling):
+        """1, 3 or 6 target pressures and couplings (natural units; Voigt xx yy zz yz xz xy for 6) -> num_p and two 6-arrays"""
+        pt = np.atleast_1d(np.asarray(p_target, dtype=np.float64)).reshape(-1)
+        pc = np.atleast_1d(np.asarray(p_coupling, dtype=np.float64)).reshape(-1)
+        if len(pt) != len(pc) or len(pt) not in (1, 3, 6):
+            raise ValueError("p_target and p_coupling need 1, 3 or 6 components each")
+        p6, c6 = np.zeros(6), np.zeros(6)
+        p6[:len(pt)], c6[:len(pc)] = pt, pc
+        return len(pt), p6, c6
+
+    def berendsen_pressure(self, box, p_target, p_coupling, thermo8, position):
+        """The barostat step of `ensemble npt_ber` (Ensemble_BER::compute2, type 11) for a host that steps by hand: from
+        find_thermo's row `thermo8` (device) the box is scaled IN PLACE (`box`: a writable float64 numpy array of 9) and the
+        positions with it; no wrap."""
+        num_p, p6, c6 = self._pressure6(p_target, p_coupling)
+        h, hp = _h9(box)
+        self._ck(self.lib.nepmi_berendsen_pressure(
+            self.handle, self.n, num_p, p6.ctypes.data_as(_capi.c_dp), c6.ctypes.data_as(_capi.c_dp), self._ptr(thermo8),
+            hp, self._ptr(position)))
+        np.asarray(box).reshape(-1)[:9] = h
+
+    def run_npt_ber(self, box, type, mass, dt, nsteps, t1, t2, t_coup, p_target, p_coupling, position, velocity, potential,
+                    force, virial, thermo_every=0):
+        """`ensemble npt_ber T1 T2 T_coup ...` (Ensemble_BER with the Berendsen barostat; p_target / p_coupling: 1, 3 or 6
+        components in natural units, p_coupling = 1 / (3 tau_p C)) -> (thermo rows like run_nve, box rows [records, 9]: the box
+        after each record step's scaling).  `box` (a writable float64 numpy array of 9) is updated in place to the final box."""
+        num_p, p6, c6 = self._pressure6(p_target, p_coupling)
+        h, hp = _h9(box)
+        if h is box or np.shares_memory(h, np.asarray(box)):
+            h = h.copy()
+            hp = h.ctypes.data_as(_capi.c_dp)
+        _, pp = _pbc3(self.pbc)
+        nrec = (nsteps // thermo_every) if thermo_every > 0 else 0
+        th = np.zeros((max(nrec, 1), 8))
+        bx = np.zeros((max(nrec, 1), 9))
+        self._ck(self.lib.nepmi_run_npt_ber(
+            self.handle, hp, pp, self.n, self._ptr(type), self._ptr(mass), float(dt), int(nsteps), float(t1),
+            float(t2), float(t_coup), num_p, p6.ctypes.data_as(_capi.c_dp), c6.ctypes.data_as(_capi.c_dp),
+            self._ptr(position), self._ptr(velocity), self._ptr(potential), self._ptr(force), self._ptr(virial),
+            int(thermo_every), th.ctypes.data_as(_capi.c_dp), bx.ctypes.data_as(_capi.c_dp)))
+        np.asarray(box).reshape(-1)[:9] = h
+        return th[:nrec], bx[:nrec]
+
+    def set_keep_lists_on_box_change(self, on=True):
+        """per-call force evaluations keep the Verlet lists across a box change (re-metric; the skin rule decides about rebuilds)"""
+        self.set_option("keep_lists_on_box_change", 1 if on else 0)
+
     NHC_STATE_SIZE = 13
 
     def nhc_init(self, temperature, t_coup, dt, chain_state):

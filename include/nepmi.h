@@ -182,6 +182,34 @@ int nepmi_run_nvt_ber(
   const double* mass, double dt, int64_t nsteps, double t1, double t2, double t_coup, double* pos,
   double* vel, double* pe, double* force, double* virial, int64_t thermo_every, double* thermo_host);
 
+/* ---- Berendsen barostat: Ensemble_BER with type 11 (src/integrate/ensemble_ber.cu:88-176, :235-284),
+ *      `ensemble npt_ber T1 T2 T_coup <pressures> <moduli> tau_p`.  num_p = 1 (isotropic), 3 (orthogonal box, one factor per
+ *      direction; a direction with pbc = 0 keeps factor 1) or 6 (triclinic, p_target / p_coupling in Voigt order xx yy zz yz xz xy);
+ *      p_target and p_coupling = 1 / (3 tau_p C) in natural units (integrate.cu:709-714, :1152-1153).  From find_thermo's row
+ *      (pressures BEFORE the velocity rescale) the factors are formed on the host with the reference's expressions in the
+ *      reference's order, h <- mu h, x <- mu x; positions are not wrapped (the next Force::compute wraps) and unwrapped positions
+ *      are not scaled.  Refused with the reference's messages (integrate.cu:649-692): num_p 1 or 3 with a triclinic box, num_p 1 or
+ *      6 with an open direction.
+ *      nepmi_berendsen_pressure: that step alone for a host that steps by hand -- thermo8 DEVICE, h HOST (in/out), pos DEVICE;
+ *      the open directions are those of the engine's last force call.
+ *      nepmi_run_npt_ber: the whole loop, the step sequence of nepmi_run_nvt_ber plus the barostat.  h is in/out (HOST): the box
+ *      to start from, the box after the last step.  thermo_host as in nepmi_run_nvt_ber (the row is taken with the volume of the
+ *      step, before either rescale); box_host (HOST, 9 doubles per record, may be NULL) receives the box AFTER that step's
+ *      scaling, what the reference's thermo.out prints next to the row.  The Verlet lists survive the box changes: the engine is
+ *      re-metricked on the host (cells, lists and window tables are integers that a homogeneous strain leaves alone) and the
+ *      lists are rebuilt by the skin rule only, whose rebuild-time positions stay in the old metric so that it counts the affine
+ *      motion like the reference's (neighbor.cu:646-684).  One look at the device per step, as in nepmi_run_nvt_bdp.  A box
+ *      in the small-box branch runs the stepwise sequence.  NEP models only; npt_scr, npt_mttk and deform are not implemented,
+ *      nor is a barostat in nepmi_dist_run. ---- */
+int nepmi_berendsen_pressure(
+  nepmi_engine* e, int64_t n, int num_p, const double p_target[6], const double p_coupling[6], const double* thermo8,
+  double h[9], double* pos);
+int nepmi_run_npt_ber(
+  nepmi_engine* e, double h[9], const int pbc[3], int64_t n, const int* type, const double* mass, double dt,
+  int64_t nsteps, double t1, double t2, double t_coup, int num_p, const double p_target[6], const double p_coupling[6],
+  double* pos, double* vel, double* pe, double* force, double* virial, int64_t thermo_every, double* thermo_host,
+  double* box_host);
+
 /* ---- Nose-Hoover chain thermostat: Ensemble_NHC (src/integrate/ensemble_nhc.cu:30-49 constructor,
  *      :102-164 nhc(), :166-232 integrate_nvt_nhc_1/2), `ensemble nvt_nhc T1 T2 T_coup`.
  *      chain_state: NEPMI_NHC_STATE_SIZE doubles of DEVICE memory owned by the caller
@@ -529,6 +557,14 @@ int nepmi_engine_set_virial_mode(nepmi_engine* e, int mode);
  *       atom is fixed, so the rebuild tabulates the windows and stores the Verlet entries as LDS slots, four to an 8-byte word
  *       (two-type models: list B as two type-pure streams); value = 0 keeps the per-launch scan of the window cells and the
  *       (window cell, rank) codes.  Same lists bit for bit, sums differ by their order only.  Forces a list rebuild.
+ *   "keep_lists_on_box_change": value = 1: a per-call force evaluation (nepmi_force_compute, nepmi_potential_compute[_levels]) whose box
+ *       differs from the last one's keeps the cells and the Verlet lists -- the engine re-metrics itself on the host and the skin
+ *       rule, with the rebuild-time positions in the old metric, decides about a rebuild like the reference's
+ *       (neighbor.cu:646-684, :741-800), so a host that runs one of the reference's NPT ensembles over this library does not pay
+ *       a rebuild per step; 0 (default): every box change rebuilds.  Applies when a valid list exists, n and pbc are unchanged
+ *       and neither box takes the small-box branch; NEP models (Tersoff engines, the split _begin/_end form and the decomposed
+ *       driver rebuild as before).  NEPMI_KEEP_LISTS=1 in the environment sets the default of every engine (a drop-in host
+ *       that does not call nepmi_engine_set_option).
  *   "stepwise_loops": Test hook: value = 1 makes nepmi_run_nvt_lan / nepmi_run_nvt_bao run as the plain sequence of the per-call steps on the caller's
  *       arrays (what they were before they became device-resident loops); the resident forms reproduce it bit for bit.
  *   "mfma": How the per-atom ANN runs.  value = 1 (default): inside the angular-descriptor kernel where the shape allows it (one
