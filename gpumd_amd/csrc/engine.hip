@@ -1591,19 +1591,24 @@ struct HipBackend {
   // angular descriptor + ANN + partial angular forces, two lanes per atom (nep_fused.h).  The kernel's LDS image lives in
   // global memory (`img`, owned by the engine; written here when `build` is set) and is copied by every workgroup.
   template <class S>
-  size_t fused_image_floats(const ModelD& md) const
+  size_t fused_image_floats(const ModelD& md, bool flat = false) const
   {
-    return (size_t)fused_lds_layout<S>(md).total;
+    return (size_t)fused_lds_layout<S>(md, 0, flat ? 1 : 0).total;
   }
+  // flat: the flat-table form of the kernel and of its image (nep_fused.h; `img` is then an image of that form)
   template <class S>
-  void launch_angular_fused(int slot, int64_t n, const ModelD& md, const Bufs& b, int export_qfp, float* img, bool build, bool pair_trip)
+  void launch_angular_fused(int slot, int64_t n, const ModelD& md, const Bufs& b, int export_qfp, float* img, bool build, bool pair_trip,
+                            bool flat = false)
   {
-    AngularFusedBody<S> body{md, b, export_qfp, nullptr};
     if (build) {
-      hipLaunchKernelGGL((nepmi_fused_image<AngularFusedBody<S>>), dim3(1), dim3(256), 0, stream, body, img);
+      if (flat)
+        hipLaunchKernelGGL((nepmi_fused_image<AngularFusedBody<S, 0, 1>>), dim3(1), dim3(256), 0, stream,
+                           AngularFusedBody<S, 0, 1>{md, b, export_qfp, nullptr}, img);
+      else
+        hipLaunchKernelGGL((nepmi_fused_image<AngularFusedBody<S>>), dim3(1), dim3(256), 0, stream,
+                           AngularFusedBody<S>{md, b, export_qfp, nullptr}, img);
       NEPMI_HIP_CHECK(hipGetLastError());
     }
-    body.img = img;
 #ifndef NEPMI_AFU_BLOCK
 #define NEPMI_AFU_BLOCK 256 // A/B switch: threads per workgroup (half as many atoms)
 #endif
@@ -1612,15 +1617,26 @@ struct HipBackend {
                          // against 2.290 -- the lockstep waiting it removes is not what the kernel's time is made of (vector issue of the heaviest
                          // wavefront of a workgroup, which the sort makes no lighter).  Off.
 #endif
-    // (the same image: the two forms differ in their record loops only.  Up to four channels per lane: with five and more the kernel
+    // (the two record-loop forms share an image.  Up to four channels per lane: with five and more the kernel
     // already spills at 256 VGPRs and the trips' second set of (g, g') adds to the scratch -- carbon 156 -> 168 B; kFusedTripMaxChannels)
-    if constexpr (FusedShape<S>::NLOC <= kFusedTripMaxChannels) {
+    constexpr bool kTrips = FusedShape<S>::NLOC <= kFusedTripMaxChannels;
+    if (flat) {
+      if constexpr (kTrips) {
+        if (pair_trip) {
+          launch_lds_pairs<NEPMI_AFU_BLOCK, AngularFusedBody<S, 1, 1>, NEPMI_AFU_SORT != 0>(slot, n, AngularFusedBody<S, 1, 1>{md, b, export_qfp, img});
+          return;
+        }
+      }
+      launch_lds_pairs<NEPMI_AFU_BLOCK, AngularFusedBody<S, 0, 1>, NEPMI_AFU_SORT != 0>(slot, n, AngularFusedBody<S, 0, 1>{md, b, export_qfp, img});
+      return;
+    }
+    if constexpr (kTrips) {
       if (pair_trip) {
         launch_lds_pairs<NEPMI_AFU_BLOCK, AngularFusedBody<S, 1>, NEPMI_AFU_SORT != 0>(slot, n, AngularFusedBody<S, 1>{md, b, export_qfp, img});
         return;
       }
     }
-    launch_lds_pairs<NEPMI_AFU_BLOCK, AngularFusedBody<S>, NEPMI_AFU_SORT != 0>(slot, n, body);
+    launch_lds_pairs<NEPMI_AFU_BLOCK, AngularFusedBody<S>, NEPMI_AFU_SORT != 0>(slot, n, AngularFusedBody<S>{md, b, export_qfp, img});
   }
 
   // ... for many-type models: type-sorted work order, a window of kFusedWindowTypes types in LDS (nepmi_fused_window_kernel)

@@ -1830,10 +1830,24 @@ private:
       fused_img_stale_ = false;
     }
   }
+  // classic_image: the caller needs the image in its first form (the per-brick kernel copies it)
   template <class S>
-  void launch_angular_fused(int export_qfp = 0)
+  void launch_angular_fused(int export_qfp = 0, bool classic_image = false)
   {
     if constexpr (B::kHasFusedAngular && S::fixed) {
+      if (ang_flat_tables_ && !classic_image) { // the flat-table form has an image of its own, built once per engine as well
+        const size_t need = be_.template fused_image_floats<S>(md_, true);
+        if (!fused_img_flat_ || fused_img_flat_floats_ < need) {
+          dfree(fused_img_flat_);
+          fused_img_flat_ = dalloc<float>(need);
+          fused_img_flat_floats_ = need;
+          fused_img_flat_stale_ = true;
+        }
+        be_.template launch_angular_fused<S>(kSlotAngular, N_, md_, b_, export_qfp, fused_img_flat_, fused_img_flat_stale_, ang_pair_trip_, true);
+        fused_img_flat_stale_ = false;
+        last_ang_flat_ = true;
+        return;
+      }
       const size_t need = be_.template fused_image_floats<S>(md_);
       if (!fused_img_ || fused_img_floats_ < need) { // (once per engine: the shape does not change)
         dfree(fused_img_);
@@ -1843,6 +1857,7 @@ private:
       }
       be_.template launch_angular_fused<S>(kSlotAngular, N_, md_, b_, export_qfp, fused_img_, fused_img_stale_, ang_pair_trip_);
       fused_img_stale_ = false;
+      last_ang_flat_ = false;
     }
   }
 
@@ -1865,7 +1880,7 @@ private:
   {
     if constexpr (B::kHasBrickForce && S::fixed && S::TS == 2) {
       if (fused_img_stale_ || !fused_img_) { // the image is written by the fused angular kernel's launcher: once, before anything
-        launch_angular_fused<S>(0);        // (a whole launch of that kernel, once per engine / temperature change)
+        launch_angular_fused<S>(0, true);  // (a whole launch of that kernel, once per engine / temperature change)
       }
       be_.template launch_brick_force<S>(kSlotAngular, kSlotForce, num_bricks_, N_, ws2, md_, halo_, fmap_, fold_rows_, step_outputs_,
                                          fused_img_, frozen);
@@ -2018,7 +2033,7 @@ public:
       b0_eff_[k] = m.b0[k] - m.w0_temp[k] * qT;
     be_.h2d(const_cast<float*>(md_.b0), b0_eff_.data(), sizeof(float) * b0_eff_.size());
     be_.ann_prepare(md_, b_); // the matrix-core weight image carries the bias as well
-    fused_img_stale_ = true;  // ... and so does the fused angular kernel's LDS image
+    fused_img_stale_ = fused_img_flat_stale_ = true; // ... and so do the fused angular kernel's LDS images
   }
   double temperature() const { return temperature_; }
   bool temperature_model() const { return model_.temperature_model; }
@@ -2043,6 +2058,7 @@ public:
     use_csync_ = o.use_csync_;
     ang_fused_ = o.ang_fused_;
     ang_pair_trip_ = o.ang_pair_trip_;
+    ang_flat_tables_ = o.ang_flat_tables_;
     fold_seam_ = o.fold_seam_;
     brick_force_ = o.brick_force_;
     loop_ctx_ = o.loop_ctx_;
@@ -2482,6 +2498,10 @@ public:
   void set_angular_pair_trip(bool on) { ang_pair_trip_ = on; }
   // ... where the shape has at most four angular channels per lane (nep_fused.h: kFusedTripMaxChannels; beyond, the trips cost scratch)
   bool ang_pair_trip_active() const { return ang_pair_trip_ && (model_.n_max_angular + 2) / 2 <= 4; }
+  // 1 (default): the per-atom phases of the fused angular kernel read a flat-table image (nep_fused.h: AngularFusedBody<S, TRIP, 1>
+  // -- bias and output weight of a neuron as one read, the radial coefficient rows of a lane's own channels as whole 16-byte
+  // groups, zero rows where lane 1 has a channel less); 0: the first image, c_rad as the model stores it.  Same bits.
+  void set_angular_flat_tables(bool on) { ang_flat_tables_ = on; }
   // 1 (default): single-domain NVE run loops fold the scatter form's window sums inside the integrator pass behind them
   // (nep_scatter.h: FoldSeamBody); 0: ForceFoldBody and ResidentStepBody as two launches.  Same bits, also across a step that a
   // window sum too large for the seam sends back to the separate kernels (run_md: no list rebuild for it).
@@ -2617,10 +2637,11 @@ public:
     s += " lanes_per_atom=" + std::to_string(tile_ok_ ? lanes : 1);
     if (last_brick_)
       s += " force=one_kernel_per_brick(descriptor+ann+partial_forces+lds_scatter_of_own_halves,lane_pairs)";
+    else if (last_ang_fused_ && last_ang_window_)
+      s += " angular=descriptor+ann+partial_forces_in_one_kernel(lane_pairs,sums_in_registers,type_sorted,window_of_4_types)";
     else if (last_ang_fused_)
-      s += last_ang_window_ ? " angular=descriptor+ann+partial_forces_in_one_kernel(lane_pairs,sums_in_registers,type_sorted,window_of_4_types)"
-                            : (ang_pair_trip_active() ? " angular=descriptor+ann+partial_forces_in_one_kernel(lane_pairs,sums_in_registers,two_record_trips)"
-                                              : " angular=descriptor+ann+partial_forces_in_one_kernel(lane_pairs,sums_in_registers)");
+      s += std::string(" angular=descriptor+ann+partial_forces_in_one_kernel(lane_pairs,sums_in_registers") +
+           (ang_pair_trip_active() ? ",two_record_trips" : "") + (last_ang_flat_ ? ",flat_tables)" : ")");
     else if (fuse_ann_active())
       s += " ann=fused_with_angular_descriptor(packed_fp32,no_mfma)";
     else if (ann_mode_ != 0 && b_.ann_img && (model_.num_types <= 4 || b_.skip_atab))
@@ -2707,6 +2728,12 @@ private:
   // set_angular_pair_trip; NEPMI_ANGULAR_PAIR_TRIP=0 in the environment: the default of engines no caller can reach (the local
   // engines of a decomposed run's ranks, tests/test_fused_pair_trip.py)
   bool ang_pair_trip_ = !(std::getenv("NEPMI_ANGULAR_PAIR_TRIP") && std::atoi(std::getenv("NEPMI_ANGULAR_PAIR_TRIP")) == 0);
+  // set_angular_flat_tables; NEPMI_ANGULAR_FLAT_TABLES=0 in the environment: the default of engines no caller can reach
+  bool ang_flat_tables_ = !(std::getenv("NEPMI_ANGULAR_FLAT_TABLES") && std::atoi(std::getenv("NEPMI_ANGULAR_FLAT_TABLES")) == 0);
+  float* fused_img_flat_ = nullptr; // the flat-table image (the first form stays in fused_img_: the per-brick kernel reads it)
+  size_t fused_img_flat_floats_ = 0;
+  bool fused_img_flat_stale_ = true;
+  bool last_ang_flat_ = false;   // the last fused angular launch (all types resident) was the flat-table form
   bool brick_force_ = false;     // set_brick_force (off: measured slower, see nep_brick.h)
   bool last_brick_ = false;      // the last force evaluation ran the per-brick force kernel
   bool brick_pending_ = false;   // ... and its partial forces / radial table have not been written to HBM since (materialise_for_gather)

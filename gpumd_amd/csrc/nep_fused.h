@@ -20,6 +20,15 @@
 //                              c_rad [T T][(n_r+1)(k_r+1)] | qscale_half [2][DPH]
 // DPH = components per lane, zero padded to a multiple of four (PbTe: 4 radial + 5 x 4 angular = 24): a weight half-row is
 // DPH / 4 ds_read_b128.
+//
+// Flat tables (AngularFusedBody<S, TRIP, 1>, engine option "angular_flat_tables"): the per-atom phases around the record loops
+// read the image in whole groups, with no lane-dependent branch between a read and the next:
+//   b0w1  [T][neuron][2]              in place of b0 | w1: a neuron's bias and output weight are one 8-byte read
+//   c_rad [T T][2][NRH][KRP]          lane `part` finds the rows of ITS channels n = part, part + 2, ... of block (t1, t2) one
+//                                     behind the other, k padded to whole 16-byte groups, the missing channel of lane 1 (odd
+//                                     channel count) a row of zeros: every read of a table row goes out before the first fma.
+// The scalers are the same block; the flat kernel reads a lane's half of them in one batch before the invariants and writes the
+// exported descriptor behind them, where the first form has a read, a wait and a branch per component.
 #pragma once
 #include "nep_window.h" // F4f
 
@@ -56,8 +65,9 @@ struct FusedLdsLayout {
 // matrix-core ANN (Bufs::tperm), a workgroup's 128 atoms span two or three types, and only those types' slices of the image
 // are staged: c_ang rows [tb, tb + TW) x T, the weight half-rows, biases and output weights of those types, the scalers.  No
 // radial table (such models' force assembly contracts from Bufs::fpr).
+// flat: the flat-table form of the image (header; all types resident only)
 template <class S>
-NEPMI_HD FusedLdsLayout fused_lds_layout(const ModelD& m, int TW = 0)
+NEPMI_HD FusedLdsLayout fused_lds_layout(const ModelD& m, int TW = 0, int flat = 0)
 {
   using F = FusedShape<S>;
   const int tw = TW > 0 ? TW : m.T;
@@ -66,6 +76,14 @@ NEPMI_HD FusedLdsLayout fused_lds_layout(const ModelD& m, int TW = 0)
   a.wstride += (8 - (a.wstride & 31) + 32) & 31; // type stride 8 mod 32 words: lanes of two types read different banks
   a.off_w = (tw * m.T * cang_stride(m) + 3) / 4 * 4;
   a.off_b0 = a.off_w + tw * a.wstride;
+  if (flat && TW == 0) {
+    constexpr int KRPC = (S::KR + 1 + 3) / 4 * 4;
+    a.off_w1 = a.off_b0 + 1; // (interleaved: b0 of neuron j at off_b0 + 2 j, w1 behind it)
+    a.off_c = (a.off_b0 + 2 * tw * m.nneu + 3) / 4 * 4;
+    a.off_qs = a.off_c + m.T * m.T * 2 * F::NRH * KRPC;
+    a.total = (a.off_qs + 2 * F::DPH + 3) / 4 * 4;
+    return a;
+  }
   a.off_w1 = a.off_b0 + tw * m.nneu;
   a.off_c = a.off_w1 + tw * m.nneu;
   a.off_qs = a.off_c + (TW > 0 ? 0 : m.T * m.T * (m.NR + 1) * (m.KR + 1));
@@ -77,7 +95,9 @@ NEPMI_HD FusedLdsLayout fused_lds_layout(const ModelD& m, int TW = 0)
 // TRIP = 1: the two record loops in trips of two records, each record's radial part evaluated by one lane of the pair instead of
 // by both (angular_s_sums_trip, pairs_from_G_trip: bit-identical results).  TRIP = 0: the one-record loops that the separate
 // kernels run as well (engine option "angular_pair_trip"; the type-window and per-brick kernels keep them).
-template <class S, int TRIP = 0>
+// FLAT = 1: the flat-table image (header); the same sums of the same operands in the same order, bit-identical results.  The
+// one term it adds -- Fp x 0 of the zero row, on lane 1 -- can only turn a half sum that is exactly -0 into +0.
+template <class S, int TRIP = 0, int FLAT = 0>
 struct AngularFusedBody {
   ModelD m;
   Bufs b;
@@ -99,8 +119,12 @@ struct AngularFusedBody {
 #endif
   static constexpr int kMinWavesPerEu = 1, kMinWavesPerEuPairs = NEPMI_AFU_WAVES;
   using F = FusedShape<S>;
+  // shapes with registers to spare after the record loops (those that take the two-record trips); the others spill already, and
+  // the flat form must not add to their scratch: they batch fewer reads (radial_rows_flat) and keep the scalers in LDS
+  static constexpr bool kRoomy = F::NLOC <= kFusedTripMaxChannels;
 
-  NEPMI_HD int lds_floats() const { return fused_lds_layout<S>(m, tw).total; }
+  NEPMI_HD FusedLdsLayout layout() const { return fused_lds_layout<S>(m, tw, FLAT); }
+  NEPMI_HD int lds_floats() const { return layout().total; }
   // the slices of types [tb, tb + nt) of the global image -> the LDS window (layout with `tw` slots)
   NEPMI_HD void stage_window(float* dst, int tb, int nt, int tid, int nth) const
   {
@@ -127,7 +151,7 @@ struct AngularFusedBody {
   NEPMI_HD void lds_stage(float* dst, int tid, int nth) const
   {
     if (img) {
-      const int n4 = (fused_lds_layout<S>(m).total + 3) / 4;
+      const int n4 = (fused_lds_layout<S>(m, 0, FLAT).total + 3) / 4;
       const F4f* __restrict__ src = reinterpret_cast<const F4f*>(img);
       F4f* d4 = reinterpret_cast<F4f*>(dst);
       for (int i = tid; i < n4; i += nth)
@@ -135,7 +159,7 @@ struct AngularFusedBody {
       return;
     }
     cang_stage(m, dst, tid, nth);
-    const FusedLdsLayout a = fused_lds_layout<S>(m);
+    const FusedLdsLayout a = fused_lds_layout<S>(m, 0, FLAT);
     const int per_t = m.nneu * 2 * F::DPH;
     for (int idx = tid; idx < m.T * per_t; idx += nth) {
       const int t = idx / per_t, r = idx - t * per_t;
@@ -144,12 +168,27 @@ struct AngularFusedBody {
       const int d = F::component(p, i);
       dst[a.off_w + t * a.wstride + r] = d >= 0 ? m.w0[((size_t)t * m.nneu + j) * m.dim + d] : 0.0f;
     }
-    for (int idx = tid; idx < m.T * m.nneu; idx += nth) {
-      dst[a.off_b0 + idx] = m.b0[idx];
-      dst[a.off_w1 + idx] = m.w1[idx];
+    if constexpr (FLAT) {
+      constexpr int KRPC = (S::KR + 1 + 3) / 4 * 4, BLK = 2 * F::NRH * KRPC;
+      for (int idx = tid; idx < m.T * m.nneu; idx += nth) {
+        dst[a.off_b0 + 2 * idx] = m.b0[idx];
+        dst[a.off_b0 + 2 * idx + 1] = m.w1[idx];
+      }
+      for (int idx = a.off_b0 + 2 * m.T * m.nneu + tid; idx < a.off_c; idx += nth)
+        dst[idx] = 0.0f;
+      for (int idx = tid; idx < m.T * m.T * BLK; idx += nth) {
+        const int blk = idx / BLK, r = idx - blk * BLK;
+        const int p = r / (F::NRH * KRPC), i = (r / KRPC) % F::NRH, kk = r % KRPC, n = 2 * i + p;
+        dst[a.off_c + idx] = (n <= S::NR && kk <= S::KR) ? m.c_rad[(blk * (S::NR + 1) + n) * (S::KR + 1) + kk] : 0.0f;
+      }
+    } else {
+      for (int idx = tid; idx < m.T * m.nneu; idx += nth) {
+        dst[a.off_b0 + idx] = m.b0[idx];
+        dst[a.off_w1 + idx] = m.w1[idx];
+      }
+      for (int idx = tid; idx < m.T * m.T * (m.NR + 1) * (m.KR + 1); idx += nth)
+        dst[a.off_c + idx] = m.c_rad[idx];
     }
-    for (int idx = tid; idx < m.T * m.T * (m.NR + 1) * (m.KR + 1); idx += nth)
-      dst[a.off_c + idx] = m.c_rad[idx];
     for (int idx = tid; idx < 2 * F::DPH; idx += nth) {
       const int d = F::component(idx / F::DPH, idx % F::DPH);
       dst[a.off_qs + idx] = d >= 0 ? m.qscale[d] : 0.0f;
@@ -174,8 +213,16 @@ struct AngularFusedBody {
   NEPMI_HD void run_window(int64_t k, int part, LP lds, int tb) const
   {
     constexpr int NLOC = F::NLOC, DPH = F::DPH;
-    if (b.lvl[k] < b.lvl_desc)
+    if constexpr (FLAT && TRIP) {
+      // The atom's level, type, slot and record count are requested together, one global round trip where the first form makes
+      // two in a row (the level, then the rest behind its test).  The test reads all four -- none of them is ever negative -- so
+      // that the loads stay in front of it; the loads of the same words further down are these.
+      const int lv = b.lvl[k], ty = b.posq[k].type, sl = b.tpos[k], na = b.nn_angstep[k];
+      if ((lv < b.lvl_desc) | ((ty | sl | na) < 0)) // (one test, not two in a row)
+        return;
+    } else if (b.lvl[k] < b.lvl_desc) {
       return;
+    }
     const int t1 = b.posq[k].type;
     LP cang = lds - tb * m.T * cang_stride(m); // (block (t1, t2) of the window sits where block (t1 - tb, t2) of a full table would)
     float s[NLOC * kNumHarm], Fp[DPH], e;
@@ -193,7 +240,9 @@ struct AngularFusedBody {
       }
     }
     // ---- radial force table A[t2][k] = sum_n Fp[n] c[t1][t2][n][k]: two half sums; lane t2 mod 2 stores row t2 ----
-    if (!b.skip_atab && tw == 0 && NEPMI_AFU_ABL != 4) {
+    if (FLAT && !b.skip_atab && tw == 0 && NEPMI_AFU_ABL != 4) {
+      radial_rows_flat(k, part, lds, t1, Fp);
+    } else if (!b.skip_atab && tw == 0 && NEPMI_AFU_ABL != 4) {
       constexpr int KRPC = (S::KR + 1 + 3) / 4 * 4; // = Bufs::KRP: rows of whole 16-byte groups
       const int KRP = b.KRP;
       for (int t2 = 0; t2 < m.T; ++t2) {
@@ -246,6 +295,82 @@ struct AngularFusedBody {
     }
   }
 
+  // The radial force table from the flat c_rad block, two rows (t2, t2 + 1) per trip: this lane's NRH table rows of both blocks
+  // are read as whole 16-byte groups before the first fma; then radial_row's chains -- i ascending from 0, one DPP add --
+  // with the zero row standing in for the channel lane 1 does not have.  Lane `part` stores row t2 + part.
+  template <class LP>
+  NEPMI_HD void radial_rows_flat(int64_t k, int part, LP lds, int t1, const float* Fp) const
+  {
+    constexpr int NRH = F::NRH;
+    constexpr int KRPC = (S::KR + 1 + 3) / 4 * 4;
+    const FusedLdsLayout a = layout();
+    const int KRP = b.KRP;
+    if constexpr (!kRoomy) {
+      // shapes whose register file is full (they spill already): one row per trip and one 16-byte group of it at a time -- NRH
+      // reads, then the group's four chains, then its store
+      for (int t2 = 0; t2 < m.T; ++t2) {
+        LP p = lds + a.off_c + ((t1 * m.T + t2) * 2 + part) * (NRH * KRPC);
+        F4f* __restrict__ out = reinterpret_cast<F4f*>(b.atab + (size_t)k * (m.T * KRP) + t2 * KRP);
+#pragma unroll
+        for (int g = 0; g < KRPC / 4; ++g) {
+          float c[NRH][4], v[4];
+#pragma unroll
+          for (int i = 0; i < NRH; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+              c[i][j] = p[i * KRPC + 4 * g + j];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            v[j] = 0.0f;
+            if (4 * g + j <= S::KR) {
+#pragma unroll
+              for (int i = 0; i < NRH; ++i)
+                v[j] = fmaf(Fp[i], c[i][j], v[j]);
+              v[j] += NEPMI_PAIR_XCHG(v[j]);
+            }
+          }
+          if ((t2 & 1) == part)
+            out[g] = F4f{v[0], v[1], v[2], v[3]};
+        }
+      }
+      return;
+    }
+    for (int t2 = 0; t2 < m.T; t2 += 2) {
+      const int t2b = t2 + 1 < m.T ? t2 + 1 : t2; // (odd type count: the last trip reads its one block twice and stores it once)
+      float c[2][NRH][KRPC];
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        LP p = lds + a.off_c + ((t1 * m.T + (u ? t2b : t2)) * 2 + part) * (NRH * KRPC);
+#pragma unroll
+        for (int i = 0; i < NRH; ++i)
+#pragma unroll
+          for (int kk = 0; kk < KRPC; ++kk)
+            c[u][i][kk] = p[i * KRPC + kk];
+      }
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        float row[KRPC];
+#pragma unroll
+        for (int kk = 0; kk < KRPC; ++kk) {
+          float v = 0.0f;
+          if (kk <= S::KR) {
+#pragma unroll
+            for (int i = 0; i < NRH; ++i)
+              v = fmaf(Fp[i], c[u][i][kk], v);
+            v += NEPMI_PAIR_XCHG(v);
+          }
+          row[kk] = v;
+        }
+        if (u == part && t2 + u < m.T) {
+          F4f* __restrict__ out = reinterpret_cast<F4f*>(b.atab + (size_t)k * (m.T * KRP) + (t2 + u) * KRP);
+#pragma unroll
+          for (int g = 0; g < KRPC / 4; ++g)
+            out[g] = F4f{row[4 * g], row[4 * g + 1], row[4 * g + 2], row[4 * g + 3]};
+        }
+      }
+    }
+  }
+
   // G = dU/ds of this lane's channels in place of their sums (invariants_adjoint with this lane's Fp rows)
   NEPMI_HD void adjoint_in_place(int part, const float* Fp, float* s) const
   {
@@ -270,7 +395,7 @@ struct AngularFusedBody {
   {
     constexpr int NRH = F::NRH, NLOC = F::NLOC, DPH = F::DPH;
     const int64_t N = b.N;
-    const FusedLdsLayout a = fused_lds_layout<S>(m, tw);
+    const FusedLdsLayout a = layout();
     const int64_t gk = b.tpos[k];
     LP QS = lds + a.off_qs + part * DPH;
 
@@ -297,6 +422,15 @@ struct AngularFusedBody {
       if (n <= S::NR)
         ql[i] = b.q[(int64_t)n * N + gk]; // radial part, written (scaled) by the radial pass
     }
+    // flat tables: this lane's scalers in whole 16-byte groups before the invariants, and the export behind them -- not a read,
+    // a wait and a branch per component
+    constexpr bool kScalersInRegisters = FLAT && kRoomy;
+    float qs[kScalersInRegisters ? DPH : 1];
+    if constexpr (kScalersInRegisters) {
+#pragma unroll
+      for (int i = 0; i < DPH; ++i)
+        qs[i] = QS[i];
+    }
 #pragma unroll
     for (int i = 0; i < NLOC; ++i) {
       const int n = part + 2 * i;
@@ -309,8 +443,23 @@ struct AngularFusedBody {
       invariants<false>(m, &s[i * kNumHarm], qn, 1);
 #pragma unroll
       for (int L = 0; L < S::NL; ++L) {
-        ql[NRH + L * NLOC + i] = qn[L] * QS[NRH + L * NLOC + i];
-        if (export_qfp)
+        if constexpr (kScalersInRegisters) {
+          ql[NRH + L * NLOC + i] = qn[L] * qs[NRH + L * NLOC + i];
+        } else {
+          ql[NRH + L * NLOC + i] = qn[L] * QS[NRH + L * NLOC + i];
+          if (export_qfp)
+            b.q[(int64_t)((S::NR + 1) + L * (S::NA + 1) + n) * N + gk] = ql[NRH + L * NLOC + i];
+        }
+      }
+    }
+    if (kScalersInRegisters && export_qfp) {
+#pragma unroll
+      for (int i = 0; i < NLOC; ++i) {
+        const int n = part + 2 * i;
+        if (n > S::NA)
+          break;
+#pragma unroll
+        for (int L = 0; L < S::NL; ++L)
           b.q[(int64_t)((S::NR + 1) + L * (S::NA + 1) + n) * N + gk] = ql[NRH + L * NLOC + i];
       }
     }
@@ -323,8 +472,10 @@ struct AngularFusedBody {
     float e = 0.0f;
     {
       LP W = lds + a.off_w + tl * a.wstride + part * DPH; // (tl: the type's slot in the LDS window)
-      LP B0 = lds + a.off_b0 + tl * m.nneu;
-      LP W1 = lds + a.off_w1 + tl * m.nneu;
+      // (flat tables: bias and output weight of neuron j side by side, one 8-byte read)
+      constexpr int BWS = FLAT ? 2 : 1;
+      LP B0 = lds + a.off_b0 + tl * (BWS * m.nneu);
+      LP W1 = FLAT ? B0 + 1 : lds + a.off_w1 + tl * m.nneu;
       // a half-row of up to 24 weights stays in the registers between the forward dot product and the backward axpy; longer
       // ones (carbon: 36) are read from LDS twice instead -- the sums and the two descriptor halves already fill the file.
       // NJ neurons per trip: their LDS reads go out together and their dot-product / tanh chains (one dependent chain each:
@@ -360,8 +511,8 @@ struct AngularFusedBody {
           const f2 acc = acc0[u] + acc1[u];
           float dot = acc.x + acc.y;
           dot += NEPMI_PAIR_XCHG(dot); // (a + b and b + a: both lanes hold the same bits)
-          const float h = ann_tanh(dot - B0[j0 + u]);
-          const float wj = W1[j0 + u];
+          const float h = ann_tanh(dot - B0[BWS * (j0 + u)]);
+          const float wj = W1[BWS * (j0 + u)];
           e = fmaf(wj, h, e);
           const f2 coef = bc2(wj * (1.0f - h * h));
 #pragma unroll

@@ -396,6 +396,12 @@ class NEP:
         (default), or one record per trip on both lanes (option "angular_pair_trip"); bit-identical results"""
         self.set_option("angular_pair_trip", 1 if on else 0)
 
+    def set_angular_flat_tables(self, on=True):
+        """per-atom phases of the fused angular kernel on the flat-table LDS image (default: bias and output weight as one
+        read, radial coefficient rows in whole 16-byte groups per lane) or on the first image (option "angular_flat_tables");
+        bit-identical results"""
+        self.set_option("angular_flat_tables", 1 if on else 0)
+
     def set_fold_seam(self, on=True):
         """single-domain NVE run loops in the scatter form: the fold of the window sums inside the integrator pass behind it
         (default), or as a launch of its own (option "fold_seam"); bit-identical results (a window sum too large for the seam

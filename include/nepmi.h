@@ -535,6 +535,14 @@ int nepmi_engine_set_virial_mode(nepmi_engine* e, int mode);
  *       (tests/test_fused_pair_trip.py).  Shapes with at most four angular channels per lane (n_max_angular <= 6): with more, the
  *       trips' second set of (g, g') spills (carbon: 156 -> 168 B of scratch) and the one-record loops stay, as they do in the
  *       type-window and per-brick forms of the kernel.
+ *   "angular_flat_tables": the LDS image that kernel's per-atom phases read: value = 1 (default) -- a neuron's bias and output weight
+ *       side by side (one 8-byte read with the weight half-row), and the radial coefficients c[t1][t2][n][k] ordered so that a lane
+ *       finds the rows of its own channels n = part, part + 2, ... one behind the other, k padded to whole 16-byte groups and the
+ *       channel count to an even one with a row of zeros: the rows of both neighbour types are read in whole groups before the first
+ *       fma of the radial force table, where the first image costs a wait per read and a lane-dependent branch per k; 0: the first
+ *       image.  The same fma chains on the same operands (the zero row adds Fp x 0 on lane 1, which can at most turn a half sum of
+ *       exactly -0 into +0): results equal under numpy.array_equal (tests/test_fused_flat_tables.py).  The type-window and per-brick
+ *       forms keep the first image.  NEPMI_ANGULAR_FLAT_TABLES=0 in the environment sets the default of engines no caller reaches.
  *   "fold_seam": Single-domain NVE run loops whose force assembly takes the scatter form: value = 1 (default) -- the fold of the
  *       window sums (one atom's entries of the up to eight brick windows that hold it) runs inside the integrator pass behind it
  *       (second half-kick of the step, and on a step that neither records thermo data nor ends the call the first half-kick, drift,
