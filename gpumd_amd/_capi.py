@@ -117,6 +117,12 @@ SYMBOLS = {
     "nepmi_engine_set_virial_mode": (C.c_int, [VP, C.c_int]),
     "nepmi_engine_describe": (C.c_int, [VP, C.c_char_p, C.c_int]),
     "nepmi_engine_set_temperature": (C.c_int, [VP, C.c_double]),
+    "nepmi_corr_create": (C.c_int, [VP, C.c_int, c_i64, c_i64, C.c_int, c_ip, C.c_int, C.POINTER(VP)]),
+    "nepmi_corr_destroy": (None, [VP]),
+    "nepmi_corr_sample": (C.c_int, [VP, VP]),
+    "nepmi_corr_attach": (C.c_int, [VP, VP]),
+    "nepmi_corr_detach": (C.c_int, [VP, VP]),
+    "nepmi_corr_read": (C.c_int, [VP, c_dp, C.POINTER(c_i64), C.POINTER(c_i64)]),
     "nepmi_transport_rccl_id": (C.c_int, [C.c_char_p]),
     "nepmi_transport_rccl": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(NepmiTransport)]),
     "nepmi_transport_tcp": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(NepmiTransport)]),

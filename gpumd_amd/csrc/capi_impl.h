@@ -30,6 +30,11 @@ struct nepmi_engine {
   nepmi::EngineT<NepmiBackend>* e;
 };
 
+struct nepmi_corr {
+  const nepmi_api* api;
+  nepmi::CorrelatorT<NepmiBackend>* c;
+};
+
 namespace {
 
 thread_local std::string g_last_error;
@@ -622,6 +627,69 @@ int nepmi_engine_set_unwrapped(nepmi_engine* e, double* d_unwrapped)
     return fail(NEPMI_ERR_ARG, "null engine");
   e->e->set_unwrapped(d_unwrapped);
   return NEPMI_OK;
+}
+
+int nepmi_corr_create(
+  nepmi_engine* e, int quantity, int64_t n, int64_t sample_interval, int num_corr, const int* group_of_atom, int num_groups,
+  nepmi_corr** out)
+{
+  if (!e || !out)
+    return fail(NEPMI_ERR_ARG, "null argument");
+  *out = nullptr;
+  nepmi_corr* c = new nepmi_corr();
+  c->api = NEPMI_SELF_API;
+  c->c = nullptr;
+  const int st = guarded([&] {
+    if (n != e->e->num_atoms())
+      throw nepmi::EngineError{NEPMI_ERR_ARG, "correlator: n is not the engine's number of atoms"};
+    c->c = new nepmi::CorrelatorT<NepmiBackend>(e->e->backend(), quantity, n, sample_interval, num_corr, group_of_atom, num_groups);
+  });
+  if (st != NEPMI_OK) {
+    delete c;
+    return st;
+  }
+  *out = c;
+  return NEPMI_OK;
+}
+
+void nepmi_corr_destroy(nepmi_corr* c)
+{
+  if (!c)
+    return;
+  if (c->c && c->c->attached_to)
+    guarded([&] { static_cast<nepmi::EngineT<NepmiBackend>*>(c->c->attached_to)->corr_detach(c->c); });
+  guarded([&] { delete c->c; });
+  delete c;
+}
+
+int nepmi_corr_sample(nepmi_corr* c, const double* q)
+{
+  if (!c || !q)
+    return fail(NEPMI_ERR_ARG, "null argument");
+  return guarded([&] { c->c->sample_now(q); });
+}
+
+int nepmi_corr_attach(nepmi_engine* e, nepmi_corr* c)
+{
+  if (!e || !c)
+    return fail(NEPMI_ERR_ARG, "null argument");
+  if (c->api != e->api)
+    return fail(NEPMI_ERR_ARG, "correlator: created from an engine of another kernel library");
+  return guarded([&] { e->e->corr_attach(c->c); });
+}
+
+int nepmi_corr_detach(nepmi_engine* e, nepmi_corr* c)
+{
+  if (!e || !c)
+    return fail(NEPMI_ERR_ARG, "null argument");
+  return guarded([&] { e->e->corr_detach(c->c); });
+}
+
+int nepmi_corr_read(nepmi_corr* c, double* sums_host, int64_t* num_origins, int64_t* num_samples)
+{
+  if (!c)
+    return fail(NEPMI_ERR_ARG, "null correlator");
+  return guarded([&] { c->c->read(sums_host, num_origins, num_samples); });
 }
 
 int nepmi_engine_set_option(nepmi_engine* e, const char* name, double value)

@@ -1203,6 +1203,24 @@ struct HipBackend {
       timer_stop(timing->slot[slot]);
   }
 
+  // correlation sums of one sample (nep_corr.h): all lags in one launch, then the fixed-order sum of the tiles' partial sums
+  static constexpr bool kHasCorr = true;
+  void launch_corr(const CorrArgs& a)
+  {
+    const int64_t grid = (int64_t)a.num_tiles * a.num_chunks, rows = (int64_t)a.num_groups * 3 * a.num_corr;
+    if (grid > 0x7fffffff || rows > 0x7fffffff)
+      throw std::runtime_error("correlator: too many tiles x lag chunks for one launch");
+    if (grid > 0) {
+      if (a.quantity == 0)
+        hipLaunchKernelGGL((nepmi_corr_tiles<0>), dim3((unsigned)grid), dim3(256), 0, stream, a, frozen);
+      else
+        hipLaunchKernelGGL((nepmi_corr_tiles<1>), dim3((unsigned)grid), dim3(256), 0, stream, a, frozen);
+      NEPMI_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(nepmi_corr_reduce, dim3((unsigned)rows), dim3(64), 0, stream, a, frozen);
+    NEPMI_HIP_CHECK(hipGetLastError());
+  }
+
   // ANN launch: the MFMA kernel when the shape fits (few types, <= 128 neurons, <= 128 output rows
   // incl. the radial-table rows), else the per-atom AnnBody.
   template <int MT, int QB, bool BYTYPE = false>

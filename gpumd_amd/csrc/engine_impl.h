@@ -7,6 +7,7 @@
 #pragma once
 #include "nep_bodies.h"
 #include "nep_md.h"
+#include "nep_corr.h"
 #include "nep_model.h"
 #include "nep_window.h"
 #include "nep_highl.h"
@@ -112,25 +113,7 @@ inline bool cover_shape_for(const NepModel& m, int out[4])
 }
 
 
-enum KernelSlot {
-  kSlotGather = 0,
-  kSlotRadial = 1,
-  kSlotAngular = 2, // angular descriptor
-  kSlotAnn = 3,
-  kSlotAngForce = 4,
-  kSlotForce = 5,
-  kSlotVV = 6,
-  kSlotThermo = 7,
-  kSlotRebuild = 8,
-  kSlotMisc = 9,
-  kNumSlots = 10
-};
 enum RegionSlot { kRegionRebuild = 0, kRegionForce = 1, kNumRegions = 2 };
-
-struct EngineError {
-  int code;
-  std::string msg;
-};
 
 inline void box_from_h9(const double h9[9], const int pbc[3], BoxD& box)
 {
@@ -258,6 +241,8 @@ public:
 
   ~EngineT()
   {
+    for (CorrelatorT<B>* c : corrs_)
+      c->attached_to = nullptr;
     for (void* p : allocs_)
       be_.free(p);
   }
@@ -736,6 +721,7 @@ public:
       explicit LoopCtx(EngineT& e_) : e(e_), was(e_.loop_ctx_) { e.loop_ctx_ = true; }
       ~LoopCtx() { e.loop_ctx_ = was; }
     } loop_ctx(*this);
+    corr_check(n);
     if ((is_small_box(box) && model_.kind == 0) || (stepwise_loops_ && (ens == kLan || ens == kBao))) {
       // (set_stepwise_loops: the Langevin ensembles as the plain sequence of the per-call entry points on the caller's
       // arrays -- what the resident forms are checked against, bit for bit)
@@ -886,7 +872,8 @@ public:
       const bool last = step + 1 == nsteps;
       step_outputs_ = record || last || npt != nullptr; // per-atom energies and virials: read at thermo records and at the exit only (NPT: the barostat reads the stresses of every step)
       b_.trip_tag = tag_of(step);     // (scatter form: a force beyond its fixed-point guard band freezes the loop at this step)
-      tersoff_defer_ = NEPMI_TERSOFF_SEAM && model_.kind == 1 && ens == kNve && !record && !last;
+      const bool vac = !corrs_.empty() && corr_vac_step(step); // like a record step for the second half-kick only: no outputs, no reduction
+      tersoff_defer_ = NEPMI_TERSOFF_SEAM && model_.kind == 1 && ens == kNve && !record && !last && !vac;
       // scatter form: the fold rides in the next pass over the atoms -- the first pass of the next step, or on a record / last step
       // the second half-kick below (the other ensembles, whose passes differ, keep the separate fold)
       // (after a veto the separate kernels for kSeamBackoffSteps steps: a veto costs a look at the flags and the steps enqueued
@@ -906,7 +893,7 @@ public:
       // synchronisation -- the speculative enqueue already hid it; what a record step costs is its work: energies and virials written,
       // the second half-kick as a pass of its own, the reduction.)
       bool need_sync = last;
-      if (ens == kNve && !record && !last) {
+      if (ens == kNve && !record && !last && !vac) {
         kick2_pending = true; // fused into the next step's pass over the atoms
       } else {
         if (fold_deferred_)
@@ -1015,8 +1002,11 @@ public:
         fold_deferred_ = false;
         continue;
       }
+      if (!corrs_.empty()) // (an MSD sample reads positions only: it ends neither the deferred second half-kick nor the deferred fold)
+        corr_sample_step(step, b_.ui, b_.vi, N_, b_.perm, frozen);
       ++step;
     }
+    corr_advance(nsteps);
     num_compute = compute0 + nsteps;
     calm_steps_ = nsteps - calm_since;
     if (virial)
@@ -1117,7 +1107,11 @@ public:
         be_.d2h(thermo_host + 8 * rec, thermo_dev_, 8 * sizeof(double));
         ++rec;
       }
+      if (!corrs_.empty()) // no internal order here: the samples come from the caller's arrays
+        corr_sample_step(step, unwrapped_, vel, n, nullptr, nullptr);
     }
+    if (nsteps > 0)
+      corr_advance(nsteps);
     be_.sync();
     int flags[kNumFlags];
     be_.d2h(flags, b_.flags, sizeof(flags));
@@ -1194,6 +1188,37 @@ public:
   }
 
 private:
+  void corr_check(int64_t n) const
+  {
+    for (const CorrelatorT<B>* c : corrs_) {
+      if (c->n() != n)
+        throw EngineError{-4, "an attached correlator was created for another number of atoms"};
+      if (c->quantity() == 0 && !unwrapped_)
+        throw EngineError{-4, "an MSD correlator is attached but the unwrapped positions are switched off"};
+    }
+  }
+  bool corr_vac_step(int64_t step) const // a VAC sample reads the velocities behind this step: its second half-kick cannot wait
+  {
+    for (const CorrelatorT<B>* c : corrs_)
+      if (c->quantity() == 1 && c->sample_index_after(step) >= 0)
+        return true;
+    return false;
+  }
+  void corr_sample_step(int64_t step, const double* u, const double* v, int64_t n, const int* perm, const int* frozen)
+  {
+    for (CorrelatorT<B>* c : corrs_) {
+      const int64_t s = c->sample_index_after(step);
+      if (s >= 0)
+        c->sample(c->quantity() == 0 ? u : v, n, perm, s, frozen);
+    }
+  }
+  void corr_advance(int64_t nsteps)
+  {
+    for (CorrelatorT<B>* c : corrs_)
+      c->advance(nsteps);
+  }
+  std::vector<CorrelatorT<B>*> corrs_;
+
   template <class T>
   T* dalloc(size_t count)
   {
@@ -2007,6 +2032,37 @@ public:
   void reset_thermostat() { nhc_fresh_ = true; }
   // caller-owned [3N] array that every first-half-step drift is also added to (atom.unwrapped_position)
   void set_unwrapped(double* u) { unwrapped_ = u; }
+  // Correlators sampled by the run loops (nep_corr.h).  After every completed step of a loop each attached correlator's step count
+  // advances, and on its sample steps the loop enqueues the gather from the internal order and the correlation kernels behind the
+  // step -- under the freeze word like every kernel of the loop, with slot, lags and origin count taken from the step number, so
+  // that a step replayed after a rebuild, a seam veto or a guard-band hand-over samples once.  The samples of a step go LAST in the
+  // step's launches: every trip freezes the state at a step before that step's force evaluation has ended (the skin check in its
+  // first pass, the scatter kernel's guard band and seam veto in its force assembly), so a sample that runs belongs to a step
+  // that stands.
+  void corr_attach(CorrelatorT<B>* c)
+  {
+    if (c->quantity() == 0 && !unwrapped_)
+      throw EngineError{-4, "an MSD correlator needs the unwrapped positions (nepmi_engine_set_unwrapped) before it is attached"};
+    if (c->n() > cap_)
+      throw EngineError{-4, "correlator: more atoms than the engine's capacity"};
+    for (CorrelatorT<B>* o : corrs_)
+      if (o == c)
+        throw EngineError{-4, "correlator: already attached"};
+    if (c->attached_to)
+      throw EngineError{-4, "correlator: attached to another engine"};
+    corrs_.push_back(c);
+    c->attached_to = this;
+  }
+  void corr_detach(CorrelatorT<B>* c)
+  {
+    for (size_t i = 0; i < corrs_.size(); ++i)
+      if (corrs_[i] == c) {
+        corrs_.erase(corrs_.begin() + i);
+        c->attached_to = nullptr;
+        return;
+      }
+    throw EngineError{-4, "correlator: not attached to this engine"};
+  }
   void check_flags_now()
   {
     int flags[kNumFlags];

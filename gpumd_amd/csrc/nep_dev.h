@@ -10,6 +10,7 @@
 #pragma once
 #include <cmath>
 #include <cstdint>
+#include <string>
 
 #include "nep_invariants_extra.h"
 
@@ -33,6 +34,27 @@
 #endif
 
 namespace nepmi {
+
+// what the engine and the objects around it throw (C ABI: code = the NEPMI_ERR_* value, msg = nepmi_last_error)
+struct EngineError {
+  int code;
+  std::string msg;
+};
+
+// timing slots of the backends' launches
+enum KernelSlot {
+  kSlotGather = 0,
+  kSlotRadial = 1,
+  kSlotAngular = 2, // angular descriptor
+  kSlotAnn = 3,
+  kSlotAngForce = 4,
+  kSlotForce = 5,
+  kSlotVV = 6,
+  kSlotThermo = 7,
+  kSlotRebuild = 8,
+  kSlotMisc = 9,
+  kNumSlots = 10
+};
 
 #if defined(__HIP_DEVICE_COMPILE__)
 // Value held by lane (l ^ MSK), MSK = 1 or 2: the lanes that share an atom are adjacent, so the exchange stays inside a quad

@@ -430,6 +430,10 @@ void Run::parse_one_keyword(const std::vector<std::string>& p)
     std::printf("    will check if uncertainties exceed %f every %d iterations.\n", a.threshold, a.interval);
     a.active = true;
     active_ = a;
+  } else if (k == "compute_msd") {
+    parse_compute_corr(p, true);
+  } else if (k == "compute_sdc") {
+    parse_compute_corr(p, false);
   } else if (k == "run") {
     if (p.size() != 2)
       input_error("run should have 1 parameter.");
@@ -446,9 +450,218 @@ void Run::parse_one_keyword(const std::vector<std::string>& p)
     dump_xyzs.clear();
     observer.active = false;
     active_.active = false;
+    msd_ = ComputeCorr();
+    sdc_ = ComputeCorr();
   } else {
     input_error("'" + k + "' is invalid keyword (or outside the path gpumd-mi covers).");
   }
+}
+
+// MSD::parse (msd.cu:481-542) and SDC::parse (sdc.cu:300-338), with their messages
+void Run::parse_compute_corr(const std::vector<std::string>& p, bool msd)
+{
+  const std::string kw = msd ? "compute_msd" : "compute_sdc";
+  std::printf(msd ? "Compute mean square displacement (MSD).\n" : "Compute self diffusion coefficient (SDC).\n");
+  ComputeCorr c;
+  c.active = true;
+  if (p.size() < 3)
+    input_error(kw + " should have at least 2 parameters.");
+  if (p.size() > (msd ? 8u : 6u))
+    input_error(kw + " has too many parameters.");
+  if (!is_valid_int(p[1], &c.interval))
+    input_error("sample interval should be an integer.");
+  if (c.interval <= 0)
+    input_error("sample interval should be positive.");
+  std::printf("    sample interval is %d.\n", c.interval);
+  if (!is_valid_int(p[2], &c.num_corr))
+    input_error("number of correlation steps should be an integer.");
+  if (c.num_corr <= 0)
+    input_error("number of correlation steps should be positive.");
+  std::printf("    number of correlation steps is %d.\n", c.num_corr);
+  auto method = [&](const std::string* tok) { // the checks parse_group and `all_groups` share (parse_utilities.cu:40-48)
+    if (!tok || !is_valid_int(*tok, &c.grouping_method))
+      input_error("Grouping method should be an integer.");
+    if (c.grouping_method < 0)
+      input_error("Grouping method should >= 0.");
+    if (c.grouping_method >= (int)groups.size())
+      input_error("Grouping method should < number of grouping methods.");
+  };
+  for (size_t m = 3; m < p.size(); ++m) {
+    if (p[m] == "group") { // parse_group, parse_utilities.cu:27-64
+      if (m + 3 > p.size())
+        input_error("Not enough arguments for option 'group'.");
+      method(&p[m + 1]);
+      if (!is_valid_int(p[m + 2], &c.group_id))
+        input_error("Group ID should be an integer.");
+      if (c.group_id >= groups[c.grouping_method].number)
+        input_error("Group ID should < number of groups.");
+      if (c.group_id < 0)
+        input_error("group ID should >= 0.");
+      std::printf("    grouping method is %d and group ID is %d.\n", c.grouping_method, c.group_id);
+      m += 2;
+    } else if (msd && p[m] == "all_groups") {
+      c.all_groups = true;
+      method(p.size() > 4 ? &p[4] : nullptr); // (msd.cu:520 reads the fifth token wherever the option stands)
+      std::printf("    will compute MSD for all groups in grouping %d.\n", c.grouping_method);
+      m += 1;
+    } else if (msd && p[m] == "save_every") {
+      if (m + 1 >= p.size() || !is_valid_int(p[m + 1], &c.save_every))
+        input_error("save_every should be an integer.");
+      std::printf("    will save a copy of the MSD every %d steps.\n", c.save_every);
+      m += 1;
+    } else {
+      input_error("Unrecognized argument in " + kw + ".");
+    }
+  }
+  if (c.all_groups && c.grouping_method >= 0 && c.group_id >= 0)
+    input_error("Cannot compute MSD over a single group and all groups at the same time");
+  (msd ? msd_ : sdc_) = c;
+}
+
+// MSD::preprocess (msd.cu:205-267) / SDC::preprocess (sdc.cu:132-155): the correlator of this run, attached to the engine
+void Run::corr_open(ComputeCorr& c, int quantity, const char* name)
+{
+  if (!c.active)
+    return;
+  // (the reference has this check for MSD only and divides by zero time origins in SDC::postprocess: refused here as well)
+  if (c.num_corr > number_of_steps / c.interval)
+    input_error(std::string(name) + " correlation times sampling interval should be <= number of MD steps.");
+  const int N = atom.number_of_atoms;
+  std::vector<int> label;
+  c.num_groups = 1;
+  if (c.grouping_method < 0) {
+    c.num_atoms = N;
+    c.atoms_per_group.assign(1, N);
+  } else if (c.all_groups) {
+    c.num_atoms = N;
+    c.num_groups = groups[c.grouping_method].number;
+    c.atoms_per_group = groups[c.grouping_method].cpu_size;
+    label = groups[c.grouping_method].cpu_label;
+  } else {
+    c.num_atoms = groups[c.grouping_method].cpu_size[c.group_id];
+    c.atoms_per_group.assign(1, c.num_atoms);
+    label.resize((size_t)N);
+    for (int i = 0; i < N; ++i)
+      label[i] = groups[c.grouping_method].cpu_label[i] == c.group_id ? 0 : -1;
+  }
+  for (int k = 0; k < 9; ++k)
+    c.cell[k] = box.cpu_h[k];
+  nepmi_engine* e = force.engine();
+  die_on(nepmi_corr_create(e, quantity, N, c.interval, c.num_corr, label.empty() ? nullptr : label.data(), c.num_groups, &c.handle),
+         name);
+  die_on(nepmi_corr_attach(e, c.handle), name);
+}
+
+void Run::corr_close(ComputeCorr& c)
+{
+  if (c.handle) {
+    die_on(nepmi_corr_detach(force.engine(), c.handle), "corr_detach");
+    nepmi_corr_destroy(c.handle);
+    c.handle = nullptr;
+  }
+}
+
+// the paths of run_segment that step by hand: measure.process behind every step
+void Run::corr_sample_stepwise()
+{
+  ++corr_steps_;
+  if (msd_.handle && corr_steps_ % msd_.interval == 0)
+    die_on(nepmi_corr_sample(msd_.handle, atom.unwrapped_position.data()), "corr_sample");
+  if (sdc_.handle && corr_steps_ % sdc_.interval == 0)
+    die_on(nepmi_corr_sample(sdc_.handle, atom.velocity_per_atom.data()), "corr_sample");
+}
+
+// MSD::write (msd.cu:365-449)
+void Run::write_msd(const char* filename)
+{
+  const ComputeCorr& c = msd_;
+  const int nc = c.num_corr, ng = c.num_groups;
+  std::vector<double> sums((size_t)ng * 3 * nc);
+  int64_t origins = 0, samples = 0;
+  die_on(nepmi_corr_read(c.handle, sums.data(), &origins, &samples), "corr_read");
+  const double dt_nat = time_step * c.interval;
+  const double dt_ps = dt_nat * TIME_UNIT_CONVERSION / 1000.0;
+  std::vector<double> msd((size_t)ng * 3 * nc, 0.0), sdc((size_t)ng * 3 * nc, 0.0);
+  for (int g = 0; g < ng; ++g) {
+    double scaler = 0.0; // empty groups, and before the first time origin
+    if (c.atoms_per_group[g] > 0 && origins > 0)
+      scaler = 1.0 / ((double)c.atoms_per_group[g] * (double)origins);
+    const double dt2inv = 0.5 / dt_nat;
+    for (int d = 0; d < 3; ++d) {
+      const size_t o = ((size_t)g * 3 + d) * nc;
+      for (int l = 0; l < nc; ++l)
+        msd[o + l] = sums[o + l] * scaler;
+      for (int l = 1; l < nc; ++l)
+        sdc[o + l] = (msd[o + l] - msd[o + l - 1]) * dt2inv;
+    }
+  }
+  const double sdc_unit_conversion = 1.0e3 / TIME_UNIT_CONVERSION;
+  FILE* fid = std::fopen(filename, "a");
+  std::fprintf(fid, "# compute_msd %d %d", c.interval, nc);
+  if (c.all_groups)
+    std::fprintf(fid, " all_groups %d", c.grouping_method);
+  else if (c.grouping_method >= 0)
+    std::fprintf(fid, " group %d %d", c.grouping_method, c.group_id);
+  if (c.save_every > 0)
+    std::fprintf(fid, " save_every %d", c.save_every);
+  std::fprintf(fid, "\n# format_version 1\n# num_atoms %d\n# num_groups %d\n# num_atoms_per_group", c.num_atoms, ng);
+  for (int g = 0; g < ng; ++g)
+    std::fprintf(fid, " %d", c.atoms_per_group[g]);
+  std::fprintf(fid, "\n# cell %.10e %.10e %.10e %.10e %.10e %.10e %.10e %.10e %.10e\n", c.cell[0], c.cell[3], c.cell[6], c.cell[1],
+               c.cell[4], c.cell[7], c.cell[2], c.cell[5], c.cell[8]);
+  std::fprintf(fid, "# dt_output %.10e ps\n# columns time_ps", dt_ps);
+  if (!c.all_groups) {
+    std::fprintf(fid, " msdx msdy msdz sdcx sdcy sdcz");
+  } else {
+    for (int g = 0; g < ng; ++g)
+      std::fprintf(fid, " msdx_%d msdy_%d msdz_%d sdcx_%d sdcy_%d sdcz_%d", g, g, g, g, g, g);
+  }
+  std::fprintf(fid, "\n");
+  for (int l = 0; l < nc; ++l) {
+    std::fprintf(fid, "%g", l * dt_ps);
+    for (int g = 0; g < ng; ++g) {
+      const size_t o = (size_t)g * 3 * nc + l;
+      std::fprintf(fid, "% g %g %g %g %g %g", msd[o], msd[o + nc], msd[o + 2 * nc], sdc[o] * sdc_unit_conversion,
+                   sdc[o + nc] * sdc_unit_conversion, sdc[o + 2 * nc] * sdc_unit_conversion);
+    }
+    std::fprintf(fid, "\n");
+  }
+  std::fclose(fid);
+}
+
+// SDC::postprocess (sdc.cu:226-292): the box of the run's end
+void Run::write_sdc()
+{
+  const ComputeCorr& c = sdc_;
+  const int nc = c.num_corr;
+  std::vector<double> vac((size_t)3 * nc);
+  int64_t origins = 0, samples = 0;
+  die_on(nepmi_corr_read(c.handle, vac.data(), &origins, &samples), "corr_read");
+  const double dt_nat = time_step * c.interval;
+  const double dt_ps = dt_nat * TIME_UNIT_CONVERSION / 1000.0;
+  const double vac_scaler = 1.0 / ((double)c.num_atoms * (double)origins);
+  for (double& v : vac)
+    v *= vac_scaler;
+  std::vector<double> sdc((size_t)3 * nc, 0.0);
+  const double dt2 = dt_nat * 0.5;
+  for (int d = 0; d < 3; ++d)
+    for (int l = 1; l < nc; ++l)
+      sdc[(size_t)d * nc + l] = sdc[(size_t)d * nc + l - 1] + (vac[(size_t)d * nc + l - 1] + vac[(size_t)d * nc + l]) * dt2;
+  const double sdc_unit_conversion = 1.0e3 / TIME_UNIT_CONVERSION;
+  const double vac_unit_conversion = sdc_unit_conversion * sdc_unit_conversion;
+  FILE* fid = std::fopen("sdc.out", "a");
+  std::fprintf(fid, "# compute_sdc %d %d", c.interval, nc);
+  if (c.grouping_method >= 0)
+    std::fprintf(fid, " group %d %d", c.grouping_method, c.group_id);
+  std::fprintf(fid, "\n# format_version 1\n# num_atoms %d\n", c.num_atoms);
+  std::fprintf(fid, "# cell %.10e %.10e %.10e %.10e %.10e %.10e %.10e %.10e %.10e\n", box.cpu_h[0], box.cpu_h[3], box.cpu_h[6],
+               box.cpu_h[1], box.cpu_h[4], box.cpu_h[7], box.cpu_h[2], box.cpu_h[5], box.cpu_h[8]);
+  std::fprintf(fid, "# dt_output %.10e ps\n# columns time_ps vacx vacy vacz sdcx sdcy sdcz\n", dt_ps);
+  for (int l = 0; l < nc; ++l)
+    std::fprintf(fid, "%g %g %g %g %g %g %g\n", l * dt_ps, vac[l] * vac_unit_conversion, vac[nc + l] * vac_unit_conversion,
+                 vac[2 * nc + l] * vac_unit_conversion, sdc[l] * sdc_unit_conversion, sdc[nc + l] * sdc_unit_conversion,
+                 sdc[2 * nc + l] * sdc_unit_conversion);
+  std::fclose(fid);
 }
 
 void Run::find_thermo()
@@ -870,6 +1083,7 @@ void Run::run_segment(int steps, double t_a, double t_b)
         die_on(nepmi_bdp_scale(e, N, target, temperature_coupling, thermo.data(), atom.velocity_per_atom.data()), "bdp");
       else if (ensemble == "nvt_nhc")
         die_on(nepmi_nhc_half_step(e, N, target, time_step, thermo.data(), nhc_state_, atom.velocity_per_atom.data()), "nhc");
+      corr_sample_stepwise();
     }
     return;
   }
@@ -918,7 +1132,7 @@ void Run::perform_a_run()
   // Dump_XYZ's constructor (dump_xyz.cu:60-63): the first dump that asks for unwrapped positions starts the
   // array from the coordinates as they are (not yet wrapped); from then on every first half-step adds its
   // drift to it (integrate.cu:347-372), in this run and the following ones
-  bool want_unwrapped = false;
+  bool want_unwrapped = msd_.active; // (MSD's constructor does the same, msd.cu:468-479)
   for (const auto& d : dump_xyzs)
     want_unwrapped = want_unwrapped || d.has_unwrapped_position;
   if (want_unwrapped && atom.unwrapped_position.size() == 0) {
@@ -936,6 +1150,9 @@ void Run::perform_a_run()
   }
   dump_observer_open(); // measure.initialize precedes the first force call (run.cu:215)
   active_open();
+  corr_steps_ = 0;
+  corr_open(msd_, 0, "MSD");
+  corr_open(sdc_, 1, "SDC");
   // target temperature of a temperature-dependent NEP (Run::parse_run, run.cu:679-681)
   // (integrate.temperature1/2 keep the values of the last ensemble that had them; an NVE-only input leaves them
   // uninitialised in the reference -- here they start at 300 K)
@@ -983,6 +1200,8 @@ void Run::perform_a_run()
     }
     if (active_.active)
       upto(active_.interval);
+    if (msd_.active)
+      upto(msd_.save_every); // msd_step<k>.out
     if (number_of_steps >= 10)
       upto(number_of_steps / 10); // progress lines
     if (correct_interval_ > 0) { // the correction precedes the steps 0, k, 2k, ...: a segment ends right before them
@@ -1007,12 +1226,22 @@ void Run::perform_a_run()
     dump_restart(step);
     dump_observer_process(step);
     active_process(step);
+    // MSD::process (msd.cu:354-359): a copy at the sample steps that are time origins and multiples of save_every
+    if (msd_.handle && msd_.save_every > 0 && done % msd_.save_every == 0 && done % msd_.interval == 0 &&
+        step / msd_.interval >= msd_.num_corr - 1)
+      write_msd(("msd_step" + std::to_string(done) + ".out").c_str());
     if (number_of_steps >= 10 && (step + 1) % (number_of_steps / 10) == 0)
       std::printf("    %d steps completed.\n", step + 1);
   }
   hip_check(hipDeviceSynchronize(), "sync");
   dump_observer_close();
   active_close();
+  if (msd_.handle)
+    write_msd("msd.out"); // MSD::postprocess
+  if (sdc_.handle)
+    write_sdc();
+  corr_close(msd_);
+  corr_close(sdc_);
   const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   std::printf("Time used for this run = %g second.\n", sec);
   std::printf("Speed of this run = %g atom*step/second.\n", (double)N * number_of_steps / sec); // run.cu:325-326
@@ -1152,6 +1381,10 @@ void Run::perform_a_run_dist()
   for (const auto& d : dump_xyzs)
     if (d.has_unwrapped_position)
       input_error("unwrapped positions are not tracked in multi-GPU runs.");
+  if (msd_.active)
+    input_error("compute_msd is not available in multi-GPU runs (unwrapped positions are not tracked there).");
+  if (sdc_.active)
+    input_error("compute_sdc is not available in multi-GPU runs.");
   const int N = atom.number_of_atoms;
   const bool root = par_.rank == 0;
   const int ens = ensemble == "nve" ? 0 : ensemble == "nvt_ber" ? 1 : ensemble == "nvt_nhc" ? 2 : ensemble == "nvt_bdp" ? 3

@@ -36,6 +36,22 @@ struct ActiveLearning {
   FILE* out_file = nullptr;  // active.out
 };
 
+// MSD (src/measure/msd.cuh) and SDC (src/measure/sdc.cuh): `compute_msd <interval> <Nc> [group <method> <id> | all_groups <method>]
+// [save_every <k>]`, `compute_sdc <interval> <Nc> [group <method> <id>]`.  The sums are libnepmi's (nepmi_corr_*), sampled inside
+// the run loops; normalisation, finite difference / trapezoid and the files are the host's.
+struct ComputeCorr {
+  bool active = false;
+  int interval = 0, num_corr = 0;
+  int grouping_method = -1, group_id = -1;
+  bool all_groups = false;
+  int save_every = 0;
+  // of the run in progress
+  nepmi_corr* handle = nullptr;
+  int num_atoms = 0, num_groups = 1;
+  std::vector<int> atoms_per_group;
+  double cell[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; // MSD::preprocess keeps the box of the run's start
+};
+
 // One process per GPU (torchrun / mpirun style launch: RANK, WORLD_SIZE, LOCAL_RANK, MASTER_ADDR, MASTER_PORT or
 // OMPI_COMM_WORLD_*): the run is domain-decomposed by libnepmi's nepmi_dist_* driver (RCCL over xGMI when every
 // rank has its own GPU, TCP sockets otherwise); rank 0 writes the output files.
@@ -72,6 +88,12 @@ private:
   void active_open();
   void active_process(int step);
   void active_close();
+  void parse_compute_corr(const std::vector<std::string>& p, bool msd);
+  void corr_open(ComputeCorr& c, int quantity, const char* name);
+  void corr_close(ComputeCorr& c);
+  void corr_sample_stepwise();
+  void write_msd(const char* filename);
+  void write_sdc();
 
   bool check_only_;
   Parallel par_;
@@ -103,6 +125,8 @@ private:
   std::vector<DumpXyz> dump_xyzs;
   DumpObserver observer;
   ActiveLearning active_;
+  ComputeCorr msd_, sdc_;
+  int corr_steps_ = 0; // finished steps of the run in progress (the paths that step by hand sample on it)
   GPU_Vector<double> thermo; // 8 doubles
   std::vector<std::string> elements;
   std::string potential_file;

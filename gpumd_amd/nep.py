@@ -7,6 +7,7 @@ public Potential`) on top of the C ABI.  Arrays are torch CUDA tensors in GPUMD'
     box                     : 9 host floats ax,bx,cx,ay,by,cy,az,bz,cz (Box::cpu_h[0..8])
 """
 import ctypes as C
+import weakref
 
 import numpy as np
 
@@ -88,6 +89,8 @@ class NEP:
         return _capi.check(self.lib, st)
 
     def close(self):
+        for c in list(getattr(self, "_correlators", ())):  # (nepmi.h: a correlator goes before its engine)
+            c.close()
         if getattr(self, "handle", None):
             self.lib.nepmi_engine_destroy(self.handle)
             self.handle = None
@@ -133,6 +136,13 @@ class NEP:
         """Atom::unwrapped_position: a [3N] f64 array that every first half-step adds its drift to (None: off)."""
         self._unwrapped = unwrapped  # keep the storage alive while the engine points at it
         self._ck(self.lib.nepmi_engine_set_unwrapped(self.handle, self._ptr(unwrapped) if unwrapped is not None else None))
+
+    def attach(self, corr):
+        """The run_* methods sample `corr` (a Correlator of this engine) every corr.interval completed steps."""
+        self._ck(self.lib.nepmi_corr_attach(self.handle, corr.handle))
+
+    def detach(self, corr):
+        self._ck(self.lib.nepmi_corr_detach(self.handle, corr.handle))
 
     def invalidate(self):
         self._ck(self.lib.nepmi_engine_invalidate(self.handle))
@@ -440,3 +450,49 @@ class NEP:
 
     def set_generic(self, on=True):
         self.set_option("generic", 1 if on else 0)
+
+
+class Correlator:
+    """Time-correlation sums (nepmi_corr_*): quantity "msd" (unwrapped positions) or "vac" (velocities), `num_corr` lags of
+    `interval` steps, optionally per group (`group_of_atom`: n ints in the caller's atom order, -1 = not sampled).
+
+    Attach it to the engine (`engine.attach(c)`) and the run_* methods sample it on the device; a host that steps by hand calls
+    `sample(q)` with q = [3N] f64 on the device.  `read()` -> (sums [num_groups, 3, num_corr], num_origins, num_samples); the
+    reader normalises: MSD_l = sums / (atoms * origins)."""
+    QUANTITIES = {"msd": 0, "vac": 1}
+
+    def __init__(self, engine, quantity, interval, num_corr, group_of_atom=None, num_groups=1):
+        self.engine = engine
+        self.lib = engine.lib
+        self.quantity = self.QUANTITIES[quantity] if isinstance(quantity, str) else int(quantity)
+        self.interval, self.num_corr, self.num_groups = int(interval), int(num_corr), int(num_groups)
+        gp = None
+        if group_of_atom is not None:
+            g = np.ascontiguousarray(np.asarray(group_of_atom), dtype=np.int32)
+            if g.shape != (engine.n,):
+                raise ValueError("group_of_atom: one int per atom")
+            gp = g.ctypes.data_as(_capi.c_ip)
+        out = C.c_void_p()
+        _capi.check(self.lib, self.lib.nepmi_corr_create(engine.handle, self.quantity, engine.n, self.interval, self.num_corr, gp,
+                                                         self.num_groups, C.byref(out)))
+        self.handle = out
+        if not hasattr(engine, "_correlators"):
+            engine._correlators = weakref.WeakSet()
+        engine._correlators.add(self)
+
+    def sample(self, q):
+        _capi.check(self.lib, self.lib.nepmi_corr_sample(self.handle, NEP._ptr(q)))
+
+    def read(self):
+        sums = np.zeros((self.num_groups, 3, self.num_corr))
+        no, ns = C.c_int64(0), C.c_int64(0)
+        _capi.check(self.lib, self.lib.nepmi_corr_read(self.handle, sums.ctypes.data_as(_capi.c_dp), C.byref(no), C.byref(ns)))
+        return sums, int(no.value), int(ns.value)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.nepmi_corr_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        self.close()

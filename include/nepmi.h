@@ -120,6 +120,32 @@ int nepmi_engine_set_external_skin(nepmi_engine* e, int on);
  * half-step (nepmi_vv_step1 and the fused nepmi_run_* loops) adds its un-wrapped drift
  * (new - old position, before the periodic wrap) to.  NULL (the default) switches it off. */
 int nepmi_engine_set_unwrapped(nepmi_engine* e, double* d_unwrapped);
+/* ---- Time-correlation sums sampled while the engine runs (replaces MSD::process, src/measure/msd.cu:269-362, and SDC::process,
+ *      src/measure/sdc.cu:157-224; the normalisation and the output belong to the reader).
+ *   quantity 0 (MSD): per component sum_i (u_i(t) - u_i(t - l))^2 over the unwrapped positions,
+ *   quantity 1 (VAC): per component sum_i  v_i(t) * v_i(t - l),               lag l = 0 .. num_corr - 1 samples.
+ * group_of_atom: HOST array of n ints in the caller's atom order, -1 = not sampled, NULL = all atoms in group 0.  The object
+ * owns, on the device, a ring of num_corr frames in an atom order of its own (by group, then by the caller's index: list
+ * rebuilds do not touch it), the sums [num_groups][3][num_corr] in double, and the counters.  Sample s = 0, 1, 2, ... goes to
+ * slot s % num_corr; from s >= num_corr - 1 on every sample is a time origin that adds, for each lag, the current frame
+ * against the frame taken that many samples earlier.  The counters run on across calls, so a host can run in segments.
+ *   _sample: one sample NOW from q = DEVICE [3][n] in the caller's order (no interval logic): for hosts that step by hand.
+ *   _attach: the nepmi_run_* loops of the engine sample the correlator themselves, every sample_interval completed steps, from
+ *            the internal-order state: no export, no synchronisation, the loop is not cut.  Several can be attached at once.
+ *            An MSD correlator needs nepmi_engine_set_unwrapped first.
+ *   _read:   sums_host (HOST, [num_groups][3][num_corr], may be NULL), time origins and samples so far.
+ * The sums are bit-reproducible run to run (no floating-point atomics).
+ * Lifetime: a correlator works on its engine's stream and staging buffers.  Destroy it (nepmi_corr_destroy, which also detaches
+ * it) BEFORE nepmi_engine_destroy of the engine it was created from; no call on it is valid after the engine is gone. ---- */
+typedef struct nepmi_corr nepmi_corr;
+int nepmi_corr_create(
+  nepmi_engine* e, int quantity, int64_t n, int64_t sample_interval, int num_corr, const int* group_of_atom, int num_groups,
+  nepmi_corr** out);
+void nepmi_corr_destroy(nepmi_corr* c);
+int nepmi_corr_sample(nepmi_corr* c, const double* q);
+int nepmi_corr_attach(nepmi_engine* e, nepmi_corr* c);
+int nepmi_corr_detach(nepmi_engine* e, nepmi_corr* c);
+int nepmi_corr_read(nepmi_corr* c, double* sums_host, int64_t* num_origins, int64_t* num_samples);
 /* The same call in two halves, so that a domain-decomposed host can overlap its ghost-position
  * exchange (the RCCL send/recv that replaces NEP_MULTIGPU's staged copies) with compute:
  *   _begin: the OWNED (level 2) entries of pos are final; ghost entries may still be in flight and
