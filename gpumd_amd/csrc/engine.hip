@@ -1414,33 +1414,37 @@ struct HipBackend {
       if constexpr (S::TS > 0) {
         const ScatterLayout lay{ws2.lay.wmax};
         const size_t lds_bytes = ((size_t)lay.bytes() + 15) / 16 * 16;
-#define NEPMI_FS_LAUNCH(OUTV, MODEV)                                                                                             \
+#define NEPMI_FS_LAUNCH(OUTV, MODEV, LEANV)                                                                                             \
   do {                                                                                                                           \
     if (lds_bytes > kBigWindowLds) { /* one workgroup per CU whatever its size: eight wavefronts (nepmi_win2_kernel) */           \
-      NEPMI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&nepmi_force_scatter_kernel<S, OUTV, MODEV, kWinThreadsBigScatter>), \
+      NEPMI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&nepmi_force_scatter_kernel<S, OUTV, MODEV, kWinThreadsBigScatter, LEANV>), \
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));                         \
-      hipLaunchKernelGGL((nepmi_force_scatter_kernel<S, OUTV, MODEV, kWinThreadsBigScatter>), dim3((unsigned)grid), dim3(kWinThreadsBigScatter), lds_bytes, \
+      hipLaunchKernelGGL((nepmi_force_scatter_kernel<S, OUTV, MODEV, kWinThreadsBigScatter, LEANV>), dim3((unsigned)grid), dim3(kWinThreadsBigScatter), lds_bytes, \
                          stream, body, nb);                                                                                     \
       break;                                                                                                                     \
     }                                                                                                                            \
     if (lds_bytes > 64 * 1024)                                                                                                   \
-      NEPMI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&nepmi_force_scatter_kernel<S, OUTV, MODEV>),           \
+      NEPMI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&nepmi_force_scatter_kernel<S, OUTV, MODEV, kWinThreads, LEANV>),           \
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));                         \
-    hipLaunchKernelGGL((nepmi_force_scatter_kernel<S, OUTV, MODEV>), dim3((unsigned)grid), dim3(kWinThreads), lds_bytes, stream, \
+    hipLaunchKernelGGL((nepmi_force_scatter_kernel<S, OUTV, MODEV, kWinThreads, LEANV>), dim3((unsigned)grid), dim3(kWinThreads), lds_bytes, stream, \
                        body, nb);                                                                                               \
   } while (0)
-        if (outputs && mode == 2)
-          NEPMI_FS_LAUNCH(true, 2);
+        if (outputs && mode == (2 | kListModeLean))
+          NEPMI_FS_LAUNCH(true, 2, 1);
+        else if (mode == (2 | kListModeLean))
+          NEPMI_FS_LAUNCH(false, 2, 1);
+        else if (outputs && mode == 2)
+          NEPMI_FS_LAUNCH(true, 2, 0);
         else if (outputs && mode == 1)
-          NEPMI_FS_LAUNCH(true, 1);
+          NEPMI_FS_LAUNCH(true, 1, 0);
         else if (outputs)
-          NEPMI_FS_LAUNCH(true, 0);
+          NEPMI_FS_LAUNCH(true, 0, 0);
         else if (mode == 2)
-          NEPMI_FS_LAUNCH(false, 2);
+          NEPMI_FS_LAUNCH(false, 2, 0);
         else if (mode == 1)
-          NEPMI_FS_LAUNCH(false, 1);
+          NEPMI_FS_LAUNCH(false, 1, 0);
         else
-          NEPMI_FS_LAUNCH(false, 0);
+          NEPMI_FS_LAUNCH(false, 0, 0);
 #undef NEPMI_FS_LAUNCH
       } else {
         // many types / run-time shapes: nepmi_force_scatter_mt_kernel, four lanes per atom, one workgroup per CU
@@ -1448,6 +1452,8 @@ struct HipBackend {
 #define NEPMI_FS_MT_LANES 4
 #endif
         constexpr int L = NEPMI_FS_MT_LANES;
+        if (mode & kListModeLean)
+          throw EngineError{-4, "launch_force_scatter: the many-type kernel has no lean body"};
         const ScatterLayoutMT lay{ws2.lay.wmax, md.T * md.T * ctab_block(md.NR, md.KR, NEPMI_FS_MT_VEC != 0)};
         const size_t lds_bytes = ((size_t)lay.bytes() + 15) / 16 * 16;
 #define NEPMI_FSMT_LAUNCH(OUTV, MODEV)                                                                                                  \

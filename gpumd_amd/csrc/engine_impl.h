@@ -2115,6 +2115,7 @@ public:
     ang_fused_ = o.ang_fused_;
     ang_pair_trip_ = o.ang_pair_trip_;
     ang_flat_tables_ = o.ang_flat_tables_;
+    lean_walks_ = o.lean_walks_;
     fold_seam_ = o.fold_seam_;
     brick_force_ = o.brick_force_;
     loop_ctx_ = o.loop_ctx_;
@@ -2234,8 +2235,12 @@ private:
       ensure_reverse_slots();
     B& rbe = radial_side_ ? *radial_side_ : be_; // (force_kernels_on: the boundary bricks on the communication stream)
     auto radial = [&](int64_t nb, int first) {
-      if (win2 && b_.use_csync)
+      if (win2 && b_.use_csync && lean_radial<S>())
+        rbe.launch_win2(kSlotRadial, nb, RadialWin2Body<S, 1, 1>{ws2, md_, first, frozen});
+      else if (win2 && b_.use_csync)
         rbe.launch_win2(kSlotRadial, nb, RadialWin2Body<S, 1>{ws2, md_, first, frozen});
+      else if (win2 && lean_radial<S>())
+        rbe.launch_win2(kSlotRadial, nb, RadialWin2Body<S, 0, 1>{ws2, md_, first, frozen});
       else if (win2)
         rbe.launch_win2(kSlotRadial, nb, RadialWin2Body<S>{ws2, md_, first, frozen});
       else if (lanes == 4)
@@ -2416,7 +2421,7 @@ private:
     return shape_ts() > 0 ? kWinMaxAtoms : kWinMaxAtomsManyType;
   }
   // how this step's radial pass left the pairs inside the cutoff (nep_scatter.h: MODE)
-  int list_mode() const { return b_.use_csync ? 2 : (b_.use_rmask ? 1 : 0); }
+  int list_mode() const { return b_.use_csync ? (lean_scatter() ? 2 | kListModeLean : 2) : (b_.use_rmask ? 1 : 0); }
   template <class S>
   bool scatter_form(const WinStage& ws2, const int* frozen)
   {
@@ -2558,6 +2563,20 @@ public:
   // -- bias and output weight of a neuron as one read, the radial coefficient rows of a lane's own channels as whole 16-byte
   // groups, zero rows where lane 1 has a channel less); 0: the first image, c_rad as the model stores it.  Same bits.
   void set_angular_flat_tables(bool on) { ang_flat_tables_ = on; }
+  // 1 (default): the two walks of the per-step radial list without the work their sums never use -- the radial pass evaluates
+  // the two candidates of a half-word of list A of a two-type shape side by side, once each (nep_window.h: RadialWin2Body<S, SYNC, 1>),
+  // and the scatter form walks the wave-synchronous words without weights or control flow for their padding places
+  // (nep_scatter.h: LEAN); 0: the former bodies.  Same bits.
+  void set_lean_list_walks(bool on) { lean_walks_ = on; }
+  // ... the radial pass: shapes with packed per-type sums (one type: the clamp only; many types are not packed)
+  template <class S>
+  bool lean_radial() const
+  {
+    return lean_walks_ && S::TS > 0;
+  }
+  // ... the scatter walk: shapes with type-pure streams (the only ones whose kernel has the lean body; the many-type kernel
+  // skips padding places altogether)
+  bool lean_scatter() const { return lean_walks_ && shape_ts() > 0; }
   // 1 (default): single-domain NVE run loops fold the scatter form's window sums inside the integrator pass behind them
   // (nep_scatter.h: FoldSeamBody); 0: ForceFoldBody and ResidentStepBody as two launches.  Same bits, also across a step that a
   // window sum too large for the seam sends back to the separate kernels (run_md: no list rebuild for it).
@@ -2708,6 +2727,7 @@ public:
       s += (shape_ != 0 && model_.n_max_angular + 1 >= 7) ? " angular_force=lane_pairs" : " angular_force=one_lane";
       s += recompute_s() ? " angular_sums=recomputed" : " angular_sums=stored";
     }
+    s += (tile_ok_ && win2 && shape_ts() > 0 && lean_walks_) ? " list_walks=lean" : " list_walks=classic";
     s += (last_scatter_form_ && last_mask_form_)   ? " radial_list=inside_bits_over_the_verlet_words"
          : (last_scatter_form_ && last_sync_form_) ? " radial_list=wave_synchronous_words"
                                                    : " radial_list=compacted";
@@ -2786,6 +2806,8 @@ private:
   bool ang_pair_trip_ = !(std::getenv("NEPMI_ANGULAR_PAIR_TRIP") && std::atoi(std::getenv("NEPMI_ANGULAR_PAIR_TRIP")) == 0);
   // set_angular_flat_tables; NEPMI_ANGULAR_FLAT_TABLES=0 in the environment: the default of engines no caller can reach
   bool ang_flat_tables_ = !(std::getenv("NEPMI_ANGULAR_FLAT_TABLES") && std::atoi(std::getenv("NEPMI_ANGULAR_FLAT_TABLES")) == 0);
+  // set_lean_list_walks; NEPMI_LEAN_LIST_WALKS=0 in the environment: the default of engines no caller can reach
+  bool lean_walks_ = !(std::getenv("NEPMI_LEAN_LIST_WALKS") && std::atoi(std::getenv("NEPMI_LEAN_LIST_WALKS")) == 0);
   float* fused_img_flat_ = nullptr; // the flat-table image (the first form stays in fused_img_: the per-brick kernel reads it)
   size_t fused_img_flat_floats_ = 0;
   bool fused_img_flat_stale_ = true;

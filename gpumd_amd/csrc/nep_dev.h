@@ -380,6 +380,20 @@ NEPMI_HD void dist_and_inv(float d2, float& d, float& dinv)
   d = d2 * dinv;
 }
 
+// min(d, rc) of a distance d >= +0 (or NaN: d2 = 0) and a cutoff rc > 0 as ONE integer minimum of their words: the order of
+// non-negative floats is the order of their words, and a NaN's word lies above every cutoff's.  The value of d < rc ? d : rc for
+// every such d (v_cmp + s_nop + v_cndmask); fminf would give it too, but costs a quieting v_max_f32 of rc per use where the
+// compiler cannot see that rc is no signalling NaN.
+NEPMI_HD float clamp_to_cutoff(float d, float rc)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+  const unsigned a = __float_as_uint(d), b = __float_as_uint(rc);
+  return __uint_as_float(a < b ? a : b);
+#else
+  return d < rc ? d : rc;
+#endif
+}
+
 // find_fc / find_fc_and_fcp, nep_utilities.cuh:409-431: fc = (1 + cos(pi d/rc)) / 2 for d < rc
 NEPMI_HD void cutoff_fc(float rcinv, float d, float& fc)
 {

@@ -159,11 +159,20 @@ __device__ __forceinline__ int to_fixed(float v)
 // only): no virial arithmetic, no pair-vector loads in the angular part, no 80 bytes of stores per atom.
 // MODE: how this step's radial pass left the list of pairs inside the cutoff -- 0 the slot-major compact list (Bufs::ccode),
 // 1 inside bits over the packed Verlet words (Bufs::rmaskA / rmaskB), 2 wave-synchronous words (SyncFifo, Bufs::cword)
-template <class S, bool OUT, int MODE>
+// LEAN (MODE 2 only; engine option "lean_list_walks"): a padding place of a word carries no control flow round its position
+// read and no float weight -- its position is read like any other (row wmax of the window: one address, a broadcast), its
+// pair-half coefficient s12 is REPLACED by 0 (one select per pair on the compare the reaction's predicate needs anyway), so
+// the range guard sees 0, the fixed-point force is the integer 0 and the virial sums take +-0, as with the weight of 0.  (The
+// envelope at min(d, rc) = rc is NOT exactly zero in general: its argument is the unrounded product of a contracted fma, and
+// e.g. for rc = 7 A the sine term comes out as -1.8e-7; nothing here relies on it.)
+// (The reaction unpredicated at the lane's OWN accumulator row, the integer 0 at distinct rows per lane, was measured and is a
+// tie with the predicate: DESIGN section 5, Round 12.)
+template <class S, bool OUT, int MODE, int LEAN = 0>
 __device__ __forceinline__ void force_scatter_atom(const ForceScatterBody<S>& B, const int64_t brick, const int64_t k,
                                                    NEPMI_LDS(char)* lds, const ScatterLayout lay)
 {
   static_assert(S::TS > 0, "type-pure list segments (one or two types with register-resident rows)");
+  static_assert(LEAN == 0 || MODE == 2, "the lean walk is a walk of the wave-synchronous words");
   constexpr bool MASK = MODE != 0; // places of weight zero exist (and touch the LDS neither for a position nor for the reaction)
   const Bufs& b = B.st.b;
   const ModelD& m = B.m;
@@ -248,11 +257,12 @@ __device__ __forceinline__ void force_scatter_atom(const ForceScatterBody<S>& B,
   };
   // two pairs side by side (packed FP32): LDS slots a0 / a1, weights w0 / w1 (0: the place adds nothing), own rows Ax / Bx / SAx
   // and pair cutoffs rc2 / ri2 per half
+  // (LEAN: live0 / live1 say which places are no padding -- a padding place's coefficient is replaced by 0; w0 / w1 are not looked at)
   auto two_pairs = [&](const unsigned a0, const unsigned a1, const float w0, const float w1, const f2* Ax, const f2* Bx, const f2 SAx,
-                       const f2 rc2, const f2 ri2) __attribute__((always_inline)) {
+                       const f2 rc2, const f2 ri2, const bool live0 = true, const bool live1 = true) __attribute__((always_inline)) {
     const unsigned o0 = row12(a0), o1 = row12(a1);
     I3 p0, p1;
-    if (MASK) {
+    if (MASK && !LEAN) {
       // a place of weight zero (a candidate outside the cutoff) touches the LDS neither for its position nor for the
       // reaction: it is evaluated at the sentinel's distance, where the envelope and its derivative vanish
       p0 = I3{ox + 0x38000000, oy, oz};
@@ -272,7 +282,8 @@ __device__ __forceinline__ void force_scatter_atom(const ForceScatterBody<S>& B,
     float d0, d1, i0, i1;
     dist_and_inv(d2.x, d0, i0);
     dist_and_inv(d2.y, d1, i1);
-    const f2 dc = mk2(d0 < rc2.x ? d0 : rc2.x, d1 < rc2.y ? d1 : rc2.y); // (a pair the exact test admitted can sit a rounding above rc)
+    // (a pair the exact test admitted can sit a rounding above rc; LEAN: one v_min_u32, the same value for every d, NaN included)
+    const f2 dc = LEAN ? mk2(clamp_to_cutoff(d0, rc2.x), clamp_to_cutoff(d1, rc2.y)) : mk2(d0 < rc2.x ? d0 : rc2.x, d1 < rc2.y ? d1 : rc2.y);
     f2 fc, fcp;
     cutoff_fc_fcp_v(ri2, dc, fc, fcp);
     const f2 dr = dc * ri2 - 1.0f;
@@ -295,10 +306,12 @@ __device__ __forceinline__ void force_scatter_atom(const ForceScatterBody<S>& B,
         u1 = u2;
       }
     }
-    const f2 s12 = vfma(dr * ri2 * 2.0f * fc, SU, fcp * 0.5f * ST); // (dx/dr fc / 2 = 2 dr fc / rc)
-    big = fmaxf(big, fmaxf(fabsf(s12.x) * w0, fabsf(s12.y) * w1));
+    f2 s12 = vfma(dr * ri2 * 2.0f * fc, SU, fcp * 0.5f * ST); // (dx/dr fc / 2 = 2 dr fc / rc)
+    if (LEAN)
+      s12 = mk2(live0 ? s12.x : 0.0f, live1 ? s12.y : 0.0f);
+    big = LEAN ? fmaxf(big, fmaxf(fabsf(s12.x), fabsf(s12.y))) : fmaxf(big, fmaxf(fabsf(s12.x) * w0, fabsf(s12.y) * w1));
     // own half of the pair force = g r12; here already in fixed-point units per grid unit of r12
-    const f2 g = s12 * mk2(i0 * (qs * w0), i1 * (qs * w1));
+    const f2 g = s12 * (LEAN ? mk2(i0 * qs, i1 * qs) : mk2(i0 * (qs * w0), i1 * (qs * w1)));
     const f2 gx = g * fx, gy = g * fy, gz = g * fz;
     if (OUT) {
       W2[0] = vfma(-fx, gx, W2[0]);
@@ -317,12 +330,12 @@ __device__ __forceinline__ void force_scatter_atom(const ForceScatterBody<S>& B,
     NEPMI_LDS(int)* r1 = (NEPMI_LDS(int)*)(wacc + o1);
     if (NEPMI_FS_ABL == 1)
       return;
-    if (!MASK || w0 != 0.0f) {
+    if (LEAN ? live0 : (!MASK || w0 != 0.0f)) { // (never at the sentinel's row: same-address LDS atomics serialise)
       lds_sub(r0, ax);
       lds_sub(r0 + 1, ay);
       lds_sub(r0 + 2, az);
     }
-    if (!MASK || w1 != 0.0f) {
+    if (LEAN ? live1 : (!MASK || w1 != 0.0f)) {
       lds_sub(r1, bx); // (compact form: the repeated entry of an odd end subtracts zero)
       lds_sub(r1 + 1, by);
       lds_sub(r1 + 2, bz);
@@ -351,8 +364,13 @@ __device__ __forceinline__ void force_scatter_atom(const ForceScatterBody<S>& B,
         cur = nxt;
         nxt = wq[(int64_t)(r + 2 < last ? r + 2 : last) * N];
         const unsigned s0 = c.lo & 0xFFFFu, s1 = c.lo >> 16, s2 = c.hi & 0xFFFFu, s3 = c.hi >> 16;
-        two_pairs(s0, s1, wgt(s0), wgt(s1), R.A, R.B, R.SA, R.rc, R.ri);
-        two_pairs(s2, s3, wgt(s2), wgt(s3), R.A, R.B, R.SA, R.rc, R.ri);
+        if (LEAN) {
+          two_pairs(s0, s1, 1.0f, 1.0f, R.A, R.B, R.SA, R.rc, R.ri, s0 != sent, s1 != sent);
+          two_pairs(s2, s3, 1.0f, 1.0f, R.A, R.B, R.SA, R.rc, R.ri, s2 != sent, s3 != sent);
+        } else {
+          two_pairs(s0, s1, wgt(s0), wgt(s1), R.A, R.B, R.SA, R.rc, R.ri);
+          two_pairs(s2, s3, wgt(s2), wgt(s3), R.A, R.B, R.SA, R.rc, R.ri);
+        }
       }
     }
   } else if constexpr (!MASK) {
@@ -584,7 +602,7 @@ __device__ __forceinline__ void force_scatter_atom(const ForceScatterBody<S>& B,
 #ifndef NEPMI_FS_WAVES
 #define NEPMI_FS_WAVES 3
 #endif
-template <class S, bool OUT, int MODE, int NT = kWinThreads>
+template <class S, bool OUT, int MODE, int NT = kWinThreads, int LEAN = 0>
 __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT > kWinThreads ? (NT + 255) / 256 : NEPMI_FS_WAVES)))
 nepmi_force_scatter_kernel(const ForceScatterBody<S> body, const int64_t nbricks)
 {
@@ -642,7 +660,7 @@ nepmi_force_scatter_kernel(const ForceScatterBody<S> body, const int64_t nbricks
   int64_t a0, a1;
   body.st.brick_range(brick, a0, a1);
   for (int64_t k = a0 + tid; k < a1; k += NT)
-    force_scatter_atom<S, OUT, MODE>(body, brick, k, lds, lay);
+    force_scatter_atom<S, OUT, MODE, LEAN>(body, brick, k, lds, lay);
   __syncthreads();
   if (NEPMI_FS_ABL != 5)
     halo_write_out<NT>(b, lds + lay.off_acc(), body.halo + (size_t)brick * lay.wmax, lay.wmax, tid);

@@ -895,7 +895,13 @@ struct SyncFifo {
   }
 };
 
-template <class S, int SYNC = 0>
+constexpr int kListModeLean = 4; // launch_force_scatter: or-ed to list mode 2 = the scatter kernel's LEAN body (nep_scatter.h)
+
+// LEAN (engine option "lean_list_walks"): list A of a two-type shape evaluates the two candidates of a half-word side by side,
+// once each, and adds each to the half of its type with a broadcast of its own half of the packed basis (the same two fma per
+// half of SS on the same operands in the same order as LEAN = 0, which evaluates every candidate in both halves); the
+// clamp of the distance is one v_min_u32 (nep_dev.h: clamp_to_cutoff).
+template <class S, int SYNC = 0, int LEAN = 0>
 struct RadialWin2Body {
   WinStage st;
   ModelD m;
@@ -1268,7 +1274,7 @@ struct RadialWin2Body {
       float d0, d1, i0, i1;
       dist_and_inv(c0.d2, d0, i0);
       dist_and_inv(c1.d2, d1, i1);
-      const f2 dc = mk2(d0 < rc0 ? d0 : rc0, d1 < rc1v ? d1 : rc1v);
+      const f2 dc = LEAN ? mk2(clamp_to_cutoff(d0, rc0), clamp_to_cutoff(d1, rc1v)) : mk2(d0 < rc0 ? d0 : rc0, d1 < rc1v ? d1 : rc1v);
       const f2 rcinv = mk2(ri0, ri1);
       f2 fc;
       cutoff_fc_v(rcinv, dc, fc);
@@ -1358,6 +1364,18 @@ struct RadialWin2Body {
 #pragma unroll
             for (int kk = 0; kk <= S::KRM; ++kk)
               SS[kk] = SS[kk] + fn[kk];
+          } else if (ZIP && LEAN) {
+            // two types, mixed order: the two candidates side by side; each half of SS takes first c[0]'s, then c[1]'s basis
+            // with the weight of its type
+            f2 fn[S::KRM + 1];
+            basis2(c[0], c[1], fn);
+            const bool one0 = ((unsigned)c[0].rw >> kIdxBits) == 1u, one1 = ((unsigned)c[1].rw >> kIdxBits) == 1u;
+            const f2 wt0 = mk2(one0 ? 0.0f : 1.0f, one0 ? 1.0f : 0.0f), wt1 = mk2(one1 ? 0.0f : 1.0f, one1 ? 1.0f : 0.0f);
+#pragma unroll
+            for (int kk = 0; kk <= S::KRM; ++kk) {
+              SS[kk] = vfma(wt0, bc2(fn[kk].x), SS[kk]);
+              SS[kk] = vfma(wt1, bc2(fn[kk].y), SS[kk]);
+            }
           } else if (ZIP) {
             // two types, mixed order: each candidate in both halves, the half of its type carries the weight (list A is a
             // quarter of the candidates; separate per-type rows would cost 28 registers over the whole kernel)

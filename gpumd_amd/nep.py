@@ -412,6 +412,12 @@ class NEP:
         bit-identical results"""
         self.set_option("angular_flat_tables", 1 if on else 0)
 
+    def set_lean_list_walks(self, on=True):
+        """the per-step radial list walked without work its sums never use (default: list A of two-type shapes evaluated once
+        per candidate in the radial pass, no weights or control flow for the padding places of the wave-synchronous words in
+        the scatter form) or by the former bodies (option "lean_list_walks"); bit-identical results"""
+        self.set_option("lean_list_walks", 1 if on else 0)
+
     def set_fold_seam(self, on=True):
         """single-domain NVE run loops in the scatter form: the fold of the window sums inside the integrator pass behind it
         (default), or as a launch of its own (option "fold_seam"); bit-identical results (a window sum too large for the seam

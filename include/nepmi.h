@@ -569,6 +569,15 @@ int nepmi_engine_set_virial_mode(nepmi_engine* e, int mode);
  *       image.  The same fma chains on the same operands (the zero row adds Fp x 0 on lane 1, which can at most turn a half sum of
  *       exactly -0 into +0): results equal under numpy.array_equal (tests/test_fused_flat_tables.py).  The type-window and per-brick
  *       forms keep the first image.  NEPMI_ANGULAR_FLAT_TABLES=0 in the environment sets the default of engines no caller reaches.
+ *   "lean_list_walks": the two kernels that walk the per-step radial list on the static window layout: value = 1 (default) -- the
+ *       radial pass evaluates the two candidates of a half-word of list A of a two-type shape side by side, once each, and adds
+ *       each to the half of its type (0: every candidate in both halves, the other type's half times 0); the scatter form walks the
+ *       wave-synchronous words with no float weight and no control flow round the position read of a padding place: its position
+ *       is read like any other and its pair coefficient is replaced by 0 with one select (0: a weight of 0 multiplied into the force
+ *       scale and the range guard, exec-mask regions round the position read).  The envelope at the sentinel's clamped distance is
+ *       not relied on (it is not exactly zero for every cutoff).  Only products with 1 and sums with 0 are left out: results equal
+ *       under numpy.array_equal for every cutoff (tests/test_lean_list_walks.py).
+ *       Many-type shapes are not touched.  NEPMI_LEAN_LIST_WALKS=0 in the environment sets the default of engines no caller reaches.
  *   "fold_seam": Single-domain NVE run loops whose force assembly takes the scatter form: value = 1 (default) -- the fold of the
  *       window sums (one atom's entries of the up to eight brick windows that hold it) runs inside the integrator pass behind it
  *       (second half-kick of the step, and on a step that neither records thermo data nor ends the call the first half-kick, drift,
