@@ -123,6 +123,14 @@ SYMBOLS = {
     "nepmi_corr_attach": (C.c_int, [VP, VP]),
     "nepmi_corr_detach": (C.c_int, [VP, VP]),
     "nepmi_corr_read": (C.c_int, [VP, c_dp, C.POINTER(c_i64), C.POINTER(c_i64)]),
+    "nepmi_rdf_create": (C.c_int, [VP, c_i64, C.c_double, C.c_int, c_i64, c_ip, C.c_int, C.POINTER(VP)]),
+    "nepmi_rdf_destroy": (None, [VP]),
+    "nepmi_rdf_sample": (C.c_int, [VP, VP, c_dp, c_ip]),
+    "nepmi_rdf_attach": (C.c_int, [VP, VP]),
+    "nepmi_rdf_detach": (C.c_int, [VP, VP]),
+    "nepmi_rdf_read": (C.c_int, [VP, C.POINTER(C.c_uint64), c_dp, C.POINTER(c_i64)]),
+    "nepmi_rdf_set_lds_budget": (C.c_int, [VP, c_i64]),
+    "nepmi_rdf_form": (C.c_int, [VP]),
     "nepmi_transport_rccl_id": (C.c_int, [C.c_char_p]),
     "nepmi_transport_rccl": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(NepmiTransport)]),
     "nepmi_transport_tcp": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(NepmiTransport)]),

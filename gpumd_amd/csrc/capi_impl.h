@@ -35,6 +35,11 @@ struct nepmi_corr {
   nepmi::CorrelatorT<NepmiBackend>* c;
 };
 
+struct nepmi_rdf {
+  const nepmi_api* api;
+  nepmi::RdfT<NepmiBackend>* r;
+};
+
 namespace {
 
 thread_local std::string g_last_error;
@@ -690,6 +695,89 @@ int nepmi_corr_read(nepmi_corr* c, double* sums_host, int64_t* num_origins, int6
   if (!c)
     return fail(NEPMI_ERR_ARG, "null correlator");
   return guarded([&] { c->c->read(sums_host, num_origins, num_samples); });
+}
+
+int nepmi_rdf_create(
+  nepmi_engine* e, int64_t n, double rc, int num_bins, int64_t sample_interval, const int* type_of_atom, int num_types,
+  nepmi_rdf** out)
+{
+  if (!e || !out)
+    return fail(NEPMI_ERR_ARG, "null argument");
+  *out = nullptr;
+  nepmi_rdf* r = new nepmi_rdf();
+  r->api = NEPMI_SELF_API;
+  r->r = nullptr;
+  const int st = guarded([&] {
+    if (n != e->e->num_atoms())
+      throw nepmi::EngineError{NEPMI_ERR_ARG, "rdf: n is not the engine's number of atoms"};
+    r->r = new nepmi::RdfT<NepmiBackend>(e->e->backend(), n, rc, num_bins, sample_interval, type_of_atom, num_types);
+  });
+  if (st != NEPMI_OK) {
+    delete r;
+    return st;
+  }
+  *out = r;
+  return NEPMI_OK;
+}
+
+void nepmi_rdf_destroy(nepmi_rdf* r)
+{
+  if (!r)
+    return;
+  if (r->r && r->r->attached_to)
+    guarded([&] { static_cast<nepmi::EngineT<NepmiBackend>*>(r->r->attached_to)->rdf_detach(r->r); });
+  guarded([&] { delete r->r; });
+  delete r;
+}
+
+int nepmi_rdf_sample(nepmi_rdf* r, const double* pos, const double* h9, const int* pbc3)
+{
+  if (!r || !pos || !h9 || !pbc3)
+    return fail(NEPMI_ERR_ARG, "null argument");
+  return guarded([&] {
+    nepmi::BoxD box;
+    nepmi::box_from_h9(h9, pbc3, box);
+    r->r->sample_now(pos, box);
+  });
+}
+
+int nepmi_rdf_attach(nepmi_engine* e, nepmi_rdf* r)
+{
+  if (!e || !r)
+    return fail(NEPMI_ERR_ARG, "null argument");
+  if (r->api != e->api)
+    return fail(NEPMI_ERR_ARG, "rdf: created from an engine of another kernel library");
+  return guarded([&] { e->e->rdf_attach(r->r); });
+}
+
+int nepmi_rdf_detach(nepmi_engine* e, nepmi_rdf* r)
+{
+  if (!e || !r)
+    return fail(NEPMI_ERR_ARG, "null argument");
+  return guarded([&] { e->e->rdf_detach(r->r); });
+}
+
+int nepmi_rdf_read(nepmi_rdf* r, uint64_t* counts_host, double* vsum_host, int64_t* num_samples)
+{
+  if (!r)
+    return fail(NEPMI_ERR_ARG, "null rdf handle");
+  static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "the counts are 64-bit");
+  return guarded([&] { r->r->read(reinterpret_cast<unsigned long long*>(counts_host), vsum_host, num_samples); });
+}
+
+int nepmi_rdf_set_lds_budget(nepmi_rdf* r, int64_t bytes)
+{
+  if (!r)
+    return fail(NEPMI_ERR_ARG, "null rdf handle");
+  r->r->set_lds_budget(bytes);
+  return NEPMI_OK;
+}
+
+int nepmi_rdf_form(nepmi_rdf* r)
+{
+  if (!r)
+    return fail(NEPMI_ERR_ARG, "null rdf handle");
+  return r->r->form();
 }
 
 int nepmi_engine_set_option(nepmi_engine* e, const char* name, double value)

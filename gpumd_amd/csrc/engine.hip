@@ -1221,6 +1221,38 @@ struct HipBackend {
     NEPMI_HIP_CHECK(hipGetLastError());
   }
 
+  // pair histogram of one RDF sample (nep_rdf.h): the cell starts, then the persistent pair kernel in the form the handle's counted
+  // rule chose (lds_hist: the workgroups' tables in LDS; else integer atomics straight to the global table)
+  static constexpr bool kHasRdf = true;
+  void launch_rdf_scan(int* data, int64_t m)
+  {
+    hipLaunchKernelGGL(nepmi_rdf_scan, dim3(1), dim3(1024), 0, stream, data, m, frozen);
+    NEPMI_HIP_CHECK(hipGetLastError());
+  }
+  template <bool LDSHIST>
+  void launch_rdf_pairs_form(const RdfArgs& a, int64_t nblocks, int words, size_t lds_bytes)
+  {
+    const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(kRdfLanesPerCu / kRdfLanes, (int64_t)(160 * 1024 / lds_bytes))); // workgroups that share a CU
+    const unsigned grid = (unsigned)std::min<int64_t>(nblocks, per_cu * 256);
+    if (lds_bytes > 64 * 1024)
+      NEPMI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&nepmi_rdf_pairs<LDSHIST>),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    hipLaunchKernelGGL((nepmi_rdf_pairs<LDSHIST>), dim3(grid), dim3(kRdfLanes), lds_bytes, stream, a, nblocks, words, frozen);
+    NEPMI_HIP_CHECK(hipGetLastError());
+  }
+  void launch_rdf_pairs(const RdfArgs& a, int64_t nblocks, bool lds_hist, int words)
+  {
+    if (nblocks <= 0)
+      return;
+    const size_t lds_bytes = (size_t)kRdfFixedLds + (lds_hist ? 4 * (size_t)words : 0);
+    if (lds_bytes > (size_t)kRdfLdsPerWorkgroup)
+      throw std::runtime_error("rdf: the LDS table does not fit");
+    if (lds_hist)
+      launch_rdf_pairs_form<true>(a, nblocks, words, lds_bytes);
+    else
+      launch_rdf_pairs_form<false>(a, nblocks, words, lds_bytes);
+  }
+
   // ANN launch: the MFMA kernel when the shape fits (few types, <= 128 neurons, <= 128 output rows
   // incl. the radial-table rows), else the per-atom AnnBody.
   template <int MT, int QB, bool BYTYPE = false>

@@ -8,6 +8,7 @@
 #include "nep_bodies.h"
 #include "nep_md.h"
 #include "nep_corr.h"
+#include "nep_rdf.h"
 #include "nep_model.h"
 #include "nep_window.h"
 #include "nep_highl.h"
@@ -722,6 +723,7 @@ public:
       ~LoopCtx() { e.loop_ctx_ = was; }
     } loop_ctx(*this);
     corr_check(n);
+    rdf_check(n);
     if ((is_small_box(box) && model_.kind == 0) || (stepwise_loops_ && (ens == kLan || ens == kBao))) {
       // (set_stepwise_loops: the Langevin ensembles as the plain sequence of the per-call entry points on the caller's
       // arrays -- what the resident forms are checked against, bit for bit)
@@ -1004,9 +1006,12 @@ public:
       }
       if (!corrs_.empty()) // (an MSD sample reads positions only: it ends neither the deferred second half-kick nor the deferred fold)
         corr_sample_step(step, b_.ui, b_.vi, N_, b_.perm, frozen);
+      if (!rdfs_.empty()) // (positions only as well; the box is the one this step ends with: under npt_ber the scaled one)
+        rdf_sample_step(step, nullptr, b_.posq, b_.perm, N_, box_, frozen);
       ++step;
     }
     corr_advance(nsteps);
+    rdf_advance(nsteps);
     num_compute = compute0 + nsteps;
     calm_steps_ = nsteps - calm_since;
     if (virial)
@@ -1109,9 +1114,13 @@ public:
       }
       if (!corrs_.empty()) // no internal order here: the samples come from the caller's arrays
         corr_sample_step(step, unwrapped_, vel, n, nullptr, nullptr);
+      if (!rdfs_.empty())
+        rdf_sample_step(step, pos, nullptr, nullptr, n, box, nullptr);
     }
-    if (nsteps > 0)
+    if (nsteps > 0) {
       corr_advance(nsteps);
+      rdf_advance(nsteps);
+    }
     be_.sync();
     int flags[kNumFlags];
     be_.d2h(flags, b_.flags, sizeof(flags));
@@ -1218,6 +1227,24 @@ private:
       c->advance(nsteps);
   }
   std::vector<CorrelatorT<B>*> corrs_;
+  void rdf_check(int64_t n) const
+  {
+    for (const RdfT<B>* r : rdfs_)
+      if (r->n() != n)
+        throw EngineError{-4, "an attached RDF handle was created for another number of atoms"};
+  }
+  void rdf_sample_step(int64_t step, const double* pos, const PosQ* posq, const int* perm, int64_t n, const BoxD& box, const int* frozen)
+  {
+    for (RdfT<B>* r : rdfs_)
+      if (r->sample_after(step))
+        r->sample(pos, posq, perm, n, box, frozen);
+  }
+  void rdf_advance(int64_t nsteps)
+  {
+    for (RdfT<B>* r : rdfs_)
+      r->advance(nsteps);
+  }
+  std::vector<RdfT<B>*> rdfs_;
 
   template <class T>
   T* dalloc(size_t count)
@@ -2062,6 +2089,31 @@ public:
         return;
       }
     throw EngineError{-4, "correlator: not attached to this engine"};
+  }
+  // RDF handles sampled by the run loops (nep_rdf.h): the rules of the correlators above -- last in the step's launches, under the
+  // freeze word, counters from the step number -- on the step's positions (internal order: an RDF does not depend on the order of the
+  // atoms) and the step's box.
+  void rdf_attach(RdfT<B>* r)
+  {
+    if (r->n() > cap_)
+      throw EngineError{-4, "rdf: more atoms than the engine's capacity"};
+    for (RdfT<B>* o : rdfs_)
+      if (o == r)
+        throw EngineError{-4, "rdf: already attached"};
+    if (r->attached_to)
+      throw EngineError{-4, "rdf: attached to another engine"};
+    rdfs_.push_back(r);
+    r->attached_to = this;
+  }
+  void rdf_detach(RdfT<B>* r)
+  {
+    for (size_t i = 0; i < rdfs_.size(); ++i)
+      if (rdfs_[i] == r) {
+        rdfs_.erase(rdfs_.begin() + i);
+        r->attached_to = nullptr;
+        return;
+      }
+    throw EngineError{-4, "rdf: not attached to this engine"};
   }
   void check_flags_now()
   {

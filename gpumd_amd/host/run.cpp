@@ -434,6 +434,8 @@ void Run::parse_one_keyword(const std::vector<std::string>& p)
     parse_compute_corr(p, true);
   } else if (k == "compute_sdc") {
     parse_compute_corr(p, false);
+  } else if (k == "compute_rdf") {
+    parse_compute_rdf(p);
   } else if (k == "run") {
     if (p.size() != 2)
       input_error("run should have 1 parameter.");
@@ -452,6 +454,7 @@ void Run::parse_one_keyword(const std::vector<std::string>& p)
     active_.active = false;
     msd_ = ComputeCorr();
     sdc_ = ComputeCorr();
+    rdf_ = ComputeRdf();
   } else {
     input_error("'" + k + "' is invalid keyword (or outside the path gpumd-mi covers).");
   }
@@ -518,6 +521,129 @@ void Run::parse_compute_corr(const std::vector<std::string>& p, bool msd)
   (msd ? msd_ : sdc_) = c;
 }
 
+// RDF::parse (rdf.cu:264-333), with its messages
+void Run::parse_compute_rdf(const std::vector<std::string>& p)
+{
+  std::printf("Compute radial distribution function (RDF).\n");
+  ComputeRdf c;
+  c.active = true;
+  if (p.size() != 4)
+    input_error("compute_rdf should have 3 parameters.");
+  if (!is_valid_real(p[1], &c.rc))
+    input_error("radial cutoff should be a number.");
+  if (c.rc <= 0)
+    input_error("radial cutoff should be positive.");
+  {
+    const double* h = box.cpu_h; // columns a, b, c
+    const double a[3] = {h[0], h[3], h[6]}, b[3] = {h[1], h[4], h[7]}, cc[3] = {h[2], h[5], h[8]};
+    auto area = [](const double* u, const double* v) {
+      const double s1 = u[1] * v[2] - u[2] * v[1], s2 = u[2] * v[0] - u[0] * v[2], s3 = u[0] * v[1] - u[1] * v[0];
+      return std::sqrt(s1 * s1 + s2 * s2 + s3 * s3);
+    };
+    const double volume = box.get_volume();
+    const double thickness_half[3] = {volume / area(b, cc) / 2.5, volume / area(cc, a) / 2.5, volume / area(a, b) / 2.5};
+    if (c.rc > thickness_half[0] || c.rc > thickness_half[1] || c.rc > thickness_half[2])
+      input_error("The box has a thickness < 2.5 RDF radial cutoffs in a periodic direction.\n"
+                  "                Please increase the periodic direction(s).");
+  }
+  std::printf("    radial cutoff %g.\n", c.rc);
+  if (!is_valid_int(p[2], &c.num_bins))
+    input_error("number of bins should be an integer.");
+  if (c.num_bins <= 20)
+    input_error("A larger nbins is recommended.");
+  if (c.num_bins > 500)
+    input_error("A smaller nbins is recommended.");
+  std::printf("    radial cutoff will be divided into %d bins.\n", c.num_bins);
+  if (!is_valid_int(p[3], &c.interval))
+    input_error("interval step per sample should be an integer.");
+  if (c.interval <= 0)
+    input_error("interval step per sample should be positive.");
+  std::printf("    RDF sample interval is %d step.\n", c.interval);
+  std::vector<int> type_size(elements.size(), 0); // atom.cpu_type_size: atoms per type of the potential
+  for (int t : atom.cpu_type)
+    if (t >= 0 && t < (int)type_size.size())
+      ++type_size[t];
+  for (size_t t = 0; t < type_size.size(); ++t)
+    if (type_size[t] != 0) {
+      c.type_index.push_back((int)t);
+      c.num_atoms.push_back(type_size[t]);
+    }
+  c.num_types = (int)c.type_index.size();
+  std::printf("    There are %d atom types in model.xyz.\n", c.num_types);
+  for (int a = 0; a < c.num_types; ++a)
+    std::printf("        Type %d has %d atoms.\n", c.type_index[a], c.num_atoms[a]);
+  std::printf("    Will calculate one total RDF and %d partial RDFs.\n", c.num_types * (c.num_types + 1) / 2);
+  rdf_ = c;
+}
+
+// RDF::preprocess (rdf.cu:163-176): the handle of this run, attached to the engine
+void Run::rdf_open()
+{
+  if (!rdf_.active)
+    return;
+  const int N = atom.number_of_atoms;
+  std::vector<int> slot(elements.size(), -1), type_of_atom((size_t)N);
+  for (int a = 0; a < rdf_.num_types; ++a)
+    slot[rdf_.type_index[a]] = a;
+  for (int i = 0; i < N; ++i)
+    type_of_atom[i] = slot[atom.cpu_type[i]];
+  nepmi_engine* e = force.engine();
+  die_on(nepmi_rdf_create(e, N, rdf_.rc, rdf_.num_bins, rdf_.interval, type_of_atom.data(), rdf_.num_types, &rdf_.handle), "RDF");
+  die_on(nepmi_rdf_attach(e, rdf_.handle), "RDF");
+}
+
+void Run::rdf_close()
+{
+  if (rdf_.handle) {
+    die_on(nepmi_rdf_detach(force.engine(), rdf_.handle), "rdf_detach");
+    nepmi_rdf_destroy(rdf_.handle);
+    rdf_.handle = nullptr;
+  }
+}
+
+// RDF::postprocess (rdf.cu:204-251) on the integer sums: the reference adds 1 / (N rho dV) per ordered pair of a sample, i.e.
+// 2 V / (N^2 dV) per unordered pair (partial a-a: 2 V / (N_a^2 dV); a-b: V / (N_a N_b dV), one order only, rdf.cu:107-112)
+void Run::write_rdf()
+{
+  const ComputeRdf& c = rdf_;
+  const int T = c.num_types, P = T * (T + 1) / 2, nb = c.num_bins;
+  std::vector<double> vsum((size_t)P * nb);
+  int64_t samples = 0;
+  die_on(nepmi_rdf_read(c.handle, nullptr, vsum.data(), &samples), "rdf_read");
+  FILE* fid = std::fopen("rdf.out", "a");
+  if (!fid)
+    input_error("Cannot open rdf.out for writing.");
+  std::vector<std::string> type_symbols((size_t)T);
+  for (int a = 0; a < T; ++a)
+    for (int n = 0; n < atom.number_of_atoms; ++n)
+      if (atom.cpu_type[n] == c.type_index[a]) {
+        type_symbols[a] = atom.cpu_atom_symbol[n];
+        break;
+      }
+  std::fprintf(fid, "#radius total");
+  for (int a = 0; a < T; ++a)
+    for (int b = a; b < T; ++b)
+      std::fprintf(fid, " %s-%s", type_symbols[a].c_str(), type_symbols[b].c_str());
+  std::fprintf(fid, "\n");
+  const int num_repeats = number_of_steps / c.interval;
+  const double dr = c.rc / nb, pi = 3.14159265358979323846, N = (double)atom.number_of_atoms;
+  for (int bin = 0; bin < nb; ++bin) {
+    const double dV = ((bin + 0.5) * dr) * ((bin + 0.5) * dr) * 4 * pi * dr;
+    double total = 0.0;
+    for (int q = 0; q < P; ++q)
+      total += vsum[(size_t)q * nb + bin];
+    std::fprintf(fid, "%.5f", bin * dr + dr / 2);
+    std::fprintf(fid, " %.5f", 2.0 * total / (N * N * dV) / num_repeats);
+    int q = 0;
+    for (int a = 0; a < T; ++a)
+      for (int b = a; b < T; ++b, ++q)
+        std::fprintf(fid, " %.5f", (a == b ? 2.0 : 1.0) * vsum[(size_t)q * nb + bin] / ((double)c.num_atoms[a] * c.num_atoms[b] * dV) / num_repeats);
+    std::fprintf(fid, "\n");
+  }
+  std::fflush(fid);
+  std::fclose(fid);
+}
+
 // MSD::preprocess (msd.cu:205-267) / SDC::preprocess (sdc.cu:132-155): the correlator of this run, attached to the engine
 void Run::corr_open(ComputeCorr& c, int quantity, const char* name)
 {
@@ -569,6 +695,10 @@ void Run::corr_sample_stepwise()
     die_on(nepmi_corr_sample(msd_.handle, atom.unwrapped_position.data()), "corr_sample");
   if (sdc_.handle && corr_steps_ % sdc_.interval == 0)
     die_on(nepmi_corr_sample(sdc_.handle, atom.velocity_per_atom.data()), "corr_sample");
+  if (rdf_.handle && corr_steps_ % rdf_.interval == 0) {
+    const int pbc[3] = {box.pbc_x, box.pbc_y, box.pbc_z};
+    die_on(nepmi_rdf_sample(rdf_.handle, atom.position_per_atom.data(), box.cpu_h, pbc), "rdf_sample");
+  }
 }
 
 // MSD::write (msd.cu:365-449)
@@ -1153,6 +1283,7 @@ void Run::perform_a_run()
   corr_steps_ = 0;
   corr_open(msd_, 0, "MSD");
   corr_open(sdc_, 1, "SDC");
+  rdf_open();
   // target temperature of a temperature-dependent NEP (Run::parse_run, run.cu:679-681)
   // (integrate.temperature1/2 keep the values of the last ensemble that had them; an NVE-only input leaves them
   // uninitialised in the reference -- here they start at 300 K)
@@ -1240,8 +1371,11 @@ void Run::perform_a_run()
     write_msd("msd.out"); // MSD::postprocess
   if (sdc_.handle)
     write_sdc();
+  if (rdf_.handle)
+    write_rdf(); // RDF::postprocess
   corr_close(msd_);
   corr_close(sdc_);
+  rdf_close();
   const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   std::printf("Time used for this run = %g second.\n", sec);
   std::printf("Speed of this run = %g atom*step/second.\n", (double)N * number_of_steps / sec); // run.cu:325-326
@@ -1385,6 +1519,8 @@ void Run::perform_a_run_dist()
     input_error("compute_msd is not available in multi-GPU runs (unwrapped positions are not tracked there).");
   if (sdc_.active)
     input_error("compute_sdc is not available in multi-GPU runs.");
+  if (rdf_.active)
+    input_error("compute_rdf is not available in multi-GPU runs.");
   const int N = atom.number_of_atoms;
   const bool root = par_.rank == 0;
   const int ens = ensemble == "nve" ? 0 : ensemble == "nvt_ber" ? 1 : ensemble == "nvt_nhc" ? 2 : ensemble == "nvt_bdp" ? 3

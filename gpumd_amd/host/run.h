@@ -52,6 +52,18 @@ struct ComputeCorr {
   double cell[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; // MSD::preprocess keeps the box of the run's start
 };
 
+// RDF (src/measure/rdf.cuh): `compute_rdf <rc> <num_bins> <interval>`.  The pair counts are libnepmi's (nepmi_rdf_*), sampled inside
+// the run loops; the normalisation and rdf.out are the host's.
+struct ComputeRdf {
+  bool active = false;
+  double rc = 0.0;
+  int num_bins = 0, interval = 0;
+  int num_types = 0;                 // types that have atoms (RDF::parse, rdf.cu:316-323)
+  std::vector<int> type_index;       // their indices in the potential's order
+  std::vector<int> num_atoms;        // and their atom counts
+  nepmi_rdf* handle = nullptr;       // of the run in progress
+};
+
 // One process per GPU (torchrun / mpirun style launch: RANK, WORLD_SIZE, LOCAL_RANK, MASTER_ADDR, MASTER_PORT or
 // OMPI_COMM_WORLD_*): the run is domain-decomposed by libnepmi's nepmi_dist_* driver (RCCL over xGMI when every
 // rank has its own GPU, TCP sockets otherwise); rank 0 writes the output files.
@@ -94,6 +106,10 @@ private:
   void corr_sample_stepwise();
   void write_msd(const char* filename);
   void write_sdc();
+  void parse_compute_rdf(const std::vector<std::string>& p);
+  void rdf_open();
+  void rdf_close();
+  void write_rdf();
 
   bool check_only_;
   Parallel par_;
@@ -126,6 +142,7 @@ private:
   DumpObserver observer;
   ActiveLearning active_;
   ComputeCorr msd_, sdc_;
+  ComputeRdf rdf_;
   int corr_steps_ = 0; // finished steps of the run in progress (the paths that step by hand sample on it)
   GPU_Vector<double> thermo; // 8 doubles
   std::vector<std::string> elements;

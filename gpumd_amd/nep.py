@@ -138,11 +138,17 @@ class NEP:
         self._ck(self.lib.nepmi_engine_set_unwrapped(self.handle, self._ptr(unwrapped) if unwrapped is not None else None))
 
     def attach(self, corr):
-        """The run_* methods sample `corr` (a Correlator of this engine) every corr.interval completed steps."""
-        self._ck(self.lib.nepmi_corr_attach(self.handle, corr.handle))
+        """The run_* methods sample `corr` (a Correlator or an RDF of this engine) every corr.interval completed steps."""
+        if isinstance(corr, RDF):
+            self._ck(self.lib.nepmi_rdf_attach(self.handle, corr.handle))
+        else:
+            self._ck(self.lib.nepmi_corr_attach(self.handle, corr.handle))
 
     def detach(self, corr):
-        self._ck(self.lib.nepmi_corr_detach(self.handle, corr.handle))
+        if isinstance(corr, RDF):
+            self._ck(self.lib.nepmi_rdf_detach(self.handle, corr.handle))
+        else:
+            self._ck(self.lib.nepmi_corr_detach(self.handle, corr.handle))
 
     def invalidate(self):
         self._ck(self.lib.nepmi_engine_invalidate(self.handle))
@@ -502,3 +508,82 @@ class Correlator:
 
     def __del__(self):
         self.close()
+
+
+class RDF:
+    """Radial distribution function as integer pair counts (nepmi_rdf_*): `num_bins` bins up to `rc`, one row per type pair
+    (a <= b; a outer, b from a), `type_of_atom`: n ints in the caller's atom order, 0 .. num_types - 1.
+
+    Attach it to the engine (`engine.attach(r)`) and the run_* methods sample it on the device every `interval` steps; a host
+    that steps by hand calls `sample(pos, h, pbc)` with pos = [3N] f64 on the device.  `read()` -> (counts [P, num_bins] uint64,
+    vsum [P, num_bins] = sum over the samples of count * volume, num_samples); `g()` normalises as the reference's rdf.out.
+    `lds_budget` (bytes) moves the threshold between the two forms of the pair kernel; `form` is 1 (tables in LDS) or 2."""
+
+    def __init__(self, engine, rc, num_bins, interval, type_of_atom, num_types, lds_budget=None):
+        self.engine = engine
+        self.lib = engine.lib
+        self.rc, self.num_bins, self.interval, self.num_types = float(rc), int(num_bins), int(interval), int(num_types)
+        self.num_pairs = self.num_types * (self.num_types + 1) // 2
+        t = np.ascontiguousarray(np.asarray(type_of_atom), dtype=np.int32)
+        if t.shape != (engine.n,):
+            raise ValueError("type_of_atom: one int per atom")
+        out = C.c_void_p()
+        _capi.check(self.lib, self.lib.nepmi_rdf_create(engine.handle, engine.n, self.rc, self.num_bins, self.interval,
+                                                        t.ctypes.data_as(_capi.c_ip), self.num_types, C.byref(out)))
+        self.handle = out
+        if not hasattr(engine, "_correlators"):
+            engine._correlators = weakref.WeakSet()
+        engine._correlators.add(self)
+        if lds_budget is not None:
+            _capi.check(self.lib, self.lib.nepmi_rdf_set_lds_budget(self.handle, int(lds_budget)))
+
+    @property
+    def form(self):
+        return _capi.check(self.lib, self.lib.nepmi_rdf_form(self.handle))
+
+    def sample(self, pos, h, pbc):
+        _, hp = _h9(h)
+        _, pp = _pbc3(pbc)
+        _capi.check(self.lib, self.lib.nepmi_rdf_sample(self.handle, NEP._ptr(pos), hp, pp))
+
+    def read(self):
+        counts = np.zeros((self.num_pairs, self.num_bins), dtype=np.uint64)
+        vsum = np.zeros((self.num_pairs, self.num_bins))
+        ns = C.c_int64(0)
+        _capi.check(self.lib, self.lib.nepmi_rdf_read(self.handle, counts.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                      vsum.ctypes.data_as(_capi.c_dp), C.byref(ns)))
+        return counts, vsum, int(ns.value)
+
+    def g(self, num_atoms_of_type, num_repeats=None):
+        """-> (r [num_bins], total [num_bins], partial [P, num_bins]), rdf.cu:107-112 and :236-243 on the integer sums;
+        num_repeats defaults to the samples taken."""
+        _, vsum, ns = self.read()
+        return rdf_normalise(vsum, self.rc, num_atoms_of_type, ns if num_repeats is None else num_repeats)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.nepmi_rdf_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        self.close()
+
+
+def rdf_normalise(vsum, rc, num_atoms_of_type, num_repeats):
+    """The one normalisation of the RDF sums: dV_w = 4 pi ((w + 0.5) dr)^2 dr, total = 2 sum_p vsum_p / (N^2 dV R),
+    partial(a, a) = 2 vsum / (N_a^2 dV R), partial(a < b) = vsum / (N_a N_b dV R)."""
+    vsum = np.asarray(vsum, dtype=np.float64)
+    na = np.asarray(num_atoms_of_type, dtype=np.float64)
+    T, nb = len(na), vsum.shape[1]
+    dr = rc / nb
+    r = (np.arange(nb) + 0.5) * dr
+    dV = 4.0 * np.pi * r * r * dr
+    R = float(num_repeats)
+    total = 2.0 * vsum.sum(axis=0) / (na.sum() ** 2 * dV * R)
+    partial = np.zeros_like(vsum)
+    p = 0
+    for a in range(T):
+        for b in range(a, T):
+            partial[p] = (2.0 if a == b else 1.0) * vsum[p] / (na[a] * na[b] * dV * R)
+            p += 1
+    return r, total, partial

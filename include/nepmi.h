@@ -146,6 +146,40 @@ int nepmi_corr_sample(nepmi_corr* c, const double* q);
 int nepmi_corr_attach(nepmi_engine* e, nepmi_corr* c);
 int nepmi_corr_detach(nepmi_engine* e, nepmi_corr* c);
 int nepmi_corr_read(nepmi_corr* c, double* sums_host, int64_t* num_origins, int64_t* num_samples);
+/* ---- Radial distribution function sampled while the engine runs (replaces RDF::process / gpu_find_rdf_ON1,
+ *      src/measure/rdf.cu:37-125, :178-202; the normalisation and the output, rdf.cu:204-251, belong to the reader).
+ * Every unordered pair of atoms at its minimum-image distance d (apply_mic, src/model/box.cuh) counts if 0 < d^2 <= rc^2, in
+ * the bin w with (w dr)^2 < d^2 <= ((w + 1) dr)^2, dr = rc / num_bins (rdf.cu:97-106).  The object owns, on the device,
+ *   counts [P][num_bins] unsigned 64-bit, P = num_types (num_types + 1) / 2 type pairs (a <= b; a outer, b from a: the order of
+ *          the reference's partial columns, rdf.cu:109-116),
+ *   vsum   [P][num_bins] double: += count of the sample * volume of the sample's box,
+ * and the sample counter.  Integer sums: exact, independent of the order of the atoms, the same bits run after run; nothing
+ * is divided on the device.  With dV_w = 4 pi ((w + 0.5) dr)^2 dr and R samples the reference's columns are
+ *   total = 2 sum_p vsum_p / (N^2 dV R),  partial(a, a) = 2 vsum / (N_a^2 dV R),  partial(a < b) = vsum / (N_a N_b dV R).
+ * type_of_atom: HOST array of n ints in the caller's atom order, 0 .. num_types - 1.
+ *   _sample: one sample NOW from pos = DEVICE [3][n] in the caller's order, wrapped or not, in the box h9 / pbc3 (HOST).
+ *   _attach: the nepmi_run_* loops of the engine sample the handle themselves after every sample_interval completed steps, from
+ *            the step's positions and the step's box (nepmi_run_npt_ber: the scaled one, as RDF::process sees it), last in the
+ *            step's launches: no export, no synchronisation, the loop is not cut.  The step count runs on across calls.
+ *   _read:   counts_host / vsum_host (HOST, [P][num_bins], either may be NULL) and the samples so far.
+ *   _set_lds_budget / _form: a TESTING AID, not for production hosts -- it exists so that both forms of the pair kernel can be
+ *            run on one input.  The kernel keeps every workgroup's table in LDS while it fits in `bytes` beside the staging
+ *            buffers (default: half a CU's 160 KB) and adds straight to the global table otherwise; _form returns which of the
+ *            two the rule chooses (1: LDS, 2: global).  Both give the same counts.
+ * Errors (NEPMI_ERR_ARG): n is not the engine's, rc <= 0, num_bins < 1, a type outside 0 .. num_types - 1, rc above thickness /
+ * 2.5 of the sample's box in any direction (rdf.cu:283-292, asked at EVERY sample), a handle attached twice or to another engine.
+ * Lifetime: as a correlator's -- destroy it BEFORE the engine it was created from. ---- */
+typedef struct nepmi_rdf nepmi_rdf;
+int nepmi_rdf_create(
+  nepmi_engine* e, int64_t n, double rc, int num_bins, int64_t sample_interval, const int* type_of_atom, int num_types,
+  nepmi_rdf** out);
+void nepmi_rdf_destroy(nepmi_rdf* rdf);
+int nepmi_rdf_sample(nepmi_rdf* rdf, const double* pos, const double* h9, const int* pbc3);
+int nepmi_rdf_attach(nepmi_engine* e, nepmi_rdf* rdf);
+int nepmi_rdf_detach(nepmi_engine* e, nepmi_rdf* rdf);
+int nepmi_rdf_read(nepmi_rdf* rdf, uint64_t* counts_host, double* vsum_host, int64_t* num_samples);
+int nepmi_rdf_set_lds_budget(nepmi_rdf* rdf, int64_t bytes);
+int nepmi_rdf_form(nepmi_rdf* rdf);
 /* The same call in two halves, so that a domain-decomposed host can overlap its ghost-position
  * exchange (the RCCL send/recv that replaces NEP_MULTIGPU's staged copies) with compute:
  *   _begin: the OWNED (level 2) entries of pos are final; ghost entries may still be in flight and
