@@ -131,6 +131,15 @@ SYMBOLS = {
     "nepmi_rdf_read": (C.c_int, [VP, C.POINTER(C.c_uint64), c_dp, C.POINTER(c_i64)]),
     "nepmi_rdf_set_lds_budget": (C.c_int, [VP, c_i64]),
     "nepmi_rdf_form": (C.c_int, [VP]),
+    "nepmi_adf_create": (C.c_int, [VP, c_i64, C.c_int, c_i64, VP, C.c_int, c_ip, C.c_int, C.POINTER(VP)]),
+    "nepmi_adf_destroy": (None, [VP]),
+    "nepmi_adf_sample": (C.c_int, [VP, VP, c_dp, c_ip]),
+    "nepmi_adf_attach": (C.c_int, [VP, VP]),
+    "nepmi_adf_detach": (C.c_int, [VP, VP]),
+    "nepmi_adf_read": (C.c_int, [VP, C.POINTER(C.c_uint64), C.POINTER(c_i64)]),
+    "nepmi_adf_set_lds_budget": (C.c_int, [VP, c_i64]),
+    "nepmi_adf_form": (C.c_int, [VP]),
+    "nepmi_adf_capacity": (C.c_int, []),
     "nepmi_transport_rccl_id": (C.c_int, [C.c_char_p]),
     "nepmi_transport_rccl": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(NepmiTransport)]),
     "nepmi_transport_tcp": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(NepmiTransport)]),

@@ -40,6 +40,11 @@ struct nepmi_rdf {
   nepmi::RdfT<NepmiBackend>* r;
 };
 
+struct nepmi_adf {
+  const nepmi_api* api;
+  nepmi::AdfT<NepmiBackend>* a;
+};
+
 namespace {
 
 thread_local std::string g_last_error;
@@ -779,6 +784,94 @@ int nepmi_rdf_form(nepmi_rdf* r)
     return fail(NEPMI_ERR_ARG, "null rdf handle");
   return r->r->form();
 }
+
+int nepmi_adf_create(
+  nepmi_engine* e, int64_t n, int num_bins, int64_t sample_interval, const nepmi_adf_row* rows, int num_rows,
+  const int* type_of_atom, int num_types, nepmi_adf** out)
+{
+  if (!e || !out)
+    return fail(NEPMI_ERR_ARG, "null argument");
+  *out = nullptr;
+  nepmi_adf* a = new nepmi_adf();
+  a->api = NEPMI_SELF_API;
+  a->a = nullptr;
+  const int st = guarded([&] {
+    if (n != e->e->num_atoms())
+      throw nepmi::EngineError{NEPMI_ERR_ARG, "adf: n is not the engine's number of atoms"};
+    std::vector<nepmi::AdfRowIn> in;
+    if (rows)
+      for (int m = 0; m < num_rows && m < nepmi::kAdfMaxRows; ++m)
+        in.push_back(nepmi::AdfRowIn{rows[m].itype, rows[m].jtype, rows[m].ktype, rows[m].rmin_j, rows[m].rmax_j, rows[m].rmin_k, rows[m].rmax_k});
+    a->a = new nepmi::AdfT<NepmiBackend>(e->e->backend(), n, num_bins, sample_interval, rows ? in.data() : nullptr, num_rows, type_of_atom, num_types);
+  });
+  if (st != NEPMI_OK) {
+    delete a;
+    return st;
+  }
+  *out = a;
+  return NEPMI_OK;
+}
+
+void nepmi_adf_destroy(nepmi_adf* a)
+{
+  if (!a)
+    return;
+  if (a->a && a->a->attached_to)
+    guarded([&] { static_cast<nepmi::EngineT<NepmiBackend>*>(a->a->attached_to)->adf_detach(a->a); });
+  guarded([&] { delete a->a; });
+  delete a;
+}
+
+int nepmi_adf_sample(nepmi_adf* a, const double* pos, const double* h9, const int* pbc3)
+{
+  if (!a || !pos || !h9 || !pbc3)
+    return fail(NEPMI_ERR_ARG, "null argument");
+  return guarded([&] {
+    nepmi::BoxD box;
+    nepmi::box_from_h9(h9, pbc3, box);
+    a->a->sample_now(pos, box);
+  });
+}
+
+int nepmi_adf_attach(nepmi_engine* e, nepmi_adf* a)
+{
+  if (!e || !a)
+    return fail(NEPMI_ERR_ARG, "null argument");
+  if (a->api != e->api)
+    return fail(NEPMI_ERR_ARG, "adf: created from an engine of another kernel library");
+  return guarded([&] { e->e->adf_attach(a->a); });
+}
+
+int nepmi_adf_detach(nepmi_engine* e, nepmi_adf* a)
+{
+  if (!e || !a)
+    return fail(NEPMI_ERR_ARG, "null argument");
+  return guarded([&] { e->e->adf_detach(a->a); });
+}
+
+int nepmi_adf_read(nepmi_adf* a, uint64_t* counts_host, int64_t* num_samples)
+{
+  if (!a)
+    return fail(NEPMI_ERR_ARG, "null adf handle");
+  return guarded([&] { a->a->read(reinterpret_cast<unsigned long long*>(counts_host), num_samples); });
+}
+
+int nepmi_adf_set_lds_budget(nepmi_adf* a, int64_t bytes)
+{
+  if (!a)
+    return fail(NEPMI_ERR_ARG, "null adf handle");
+  a->a->set_lds_budget(bytes);
+  return NEPMI_OK;
+}
+
+int nepmi_adf_form(nepmi_adf* a)
+{
+  if (!a)
+    return fail(NEPMI_ERR_ARG, "null adf handle");
+  return a->a->form();
+}
+
+int nepmi_adf_capacity(void) { return nepmi::kAdfMaxNeighbours; }
 
 int nepmi_engine_set_option(nepmi_engine* e, const char* name, double value)
 {

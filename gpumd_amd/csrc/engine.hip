@@ -1253,6 +1253,41 @@ struct HipBackend {
       launch_rdf_pairs_form<false>(a, nblocks, words, lds_bytes);
   }
 
+  // triplet histogram of one ADF sample (nep_adf.h), in the form the handle's counted rule chose
+  static constexpr bool kHasAdf = true;
+  void launch_adf_scan(int* data, int64_t m, int* tile_sums)
+  {
+    const int64_t tiles = (m + kAdfScanTile - 1) / kAdfScanTile;
+    hipLaunchKernelGGL(nepmi_adf_scan_tiles, dim3((unsigned)tiles), dim3(1024), 0, stream, data, m, tile_sums, frozen);
+    NEPMI_HIP_CHECK(hipGetLastError());
+    launch_rdf_scan(tile_sums, tiles);
+    hipLaunchKernelGGL(nepmi_adf_scan_add, dim3((unsigned)tiles), dim3(1024), 0, stream, data, m, (const int*)tile_sums, frozen);
+    NEPMI_HIP_CHECK(hipGetLastError());
+  }
+  template <bool LDSHIST>
+  void launch_adf_triplets_form(const AdfArgs& a, int64_t n, int words, size_t lds_bytes)
+  {
+    const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(kRdfLanesPerCu / kAdfLanes, (int64_t)(160 * 1024 / lds_bytes))); // workgroups that share a CU
+    const unsigned grid = (unsigned)std::min<int64_t>((n + kAdfWaves - 1) / kAdfWaves, per_cu * 256);
+    if (lds_bytes > 64 * 1024)
+      NEPMI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&nepmi_adf_triplets<LDSHIST>),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    hipLaunchKernelGGL((nepmi_adf_triplets<LDSHIST>), dim3(grid), dim3(kAdfLanes), lds_bytes, stream, a, n, words, frozen);
+    NEPMI_HIP_CHECK(hipGetLastError());
+  }
+  void launch_adf_triplets(const AdfArgs& a, int64_t n, bool lds_hist, int words)
+  {
+    if (n <= 0)
+      return;
+    const size_t lds_bytes = (size_t)adf_lds_fixed(a.num_bins) + (lds_hist ? 4 * (size_t)words : 0);
+    if (lds_bytes > (size_t)kAdfLdsPerCu)
+      throw std::runtime_error("adf: the LDS table does not fit");
+    if (lds_hist)
+      launch_adf_triplets_form<true>(a, n, words, lds_bytes);
+    else
+      launch_adf_triplets_form<false>(a, n, words, lds_bytes);
+  }
+
   // ANN launch: the MFMA kernel when the shape fits (few types, <= 128 neurons, <= 128 output rows
   // incl. the radial-table rows), else the per-atom AnnBody.
   template <int MT, int QB, bool BYTYPE = false>

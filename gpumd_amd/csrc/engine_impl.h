@@ -9,6 +9,7 @@
 #include "nep_md.h"
 #include "nep_corr.h"
 #include "nep_rdf.h"
+#include "nep_adf.h"
 #include "nep_model.h"
 #include "nep_window.h"
 #include "nep_highl.h"
@@ -724,6 +725,7 @@ public:
     } loop_ctx(*this);
     corr_check(n);
     rdf_check(n);
+    adf_check(n);
     if ((is_small_box(box) && model_.kind == 0) || (stepwise_loops_ && (ens == kLan || ens == kBao))) {
       // (set_stepwise_loops: the Langevin ensembles as the plain sequence of the per-call entry points on the caller's
       // arrays -- what the resident forms are checked against, bit for bit)
@@ -1008,10 +1010,13 @@ public:
         corr_sample_step(step, b_.ui, b_.vi, N_, b_.perm, frozen);
       if (!rdfs_.empty()) // (positions only as well; the box is the one this step ends with: under npt_ber the scaled one)
         rdf_sample_step(step, nullptr, b_.posq, b_.perm, N_, box_, frozen);
+      if (!adfs_.empty()) // (last of the step's launches; positions only, the step's box)
+        adf_sample_step(step, nullptr, b_.posq, b_.perm, N_, box_, frozen);
       ++step;
     }
     corr_advance(nsteps);
     rdf_advance(nsteps);
+    adf_advance(nsteps);
     num_compute = compute0 + nsteps;
     calm_steps_ = nsteps - calm_since;
     if (virial)
@@ -1116,10 +1121,13 @@ public:
         corr_sample_step(step, unwrapped_, vel, n, nullptr, nullptr);
       if (!rdfs_.empty())
         rdf_sample_step(step, pos, nullptr, nullptr, n, box, nullptr);
+      if (!adfs_.empty())
+        adf_sample_step(step, pos, nullptr, nullptr, n, box, nullptr);
     }
     if (nsteps > 0) {
       corr_advance(nsteps);
       rdf_advance(nsteps);
+      adf_advance(nsteps);
     }
     be_.sync();
     int flags[kNumFlags];
@@ -1245,6 +1253,24 @@ private:
       r->advance(nsteps);
   }
   std::vector<RdfT<B>*> rdfs_;
+  void adf_check(int64_t n) const
+  {
+    for (const AdfT<B>* r : adfs_)
+      if (r->n() != n)
+        throw EngineError{-4, "an attached ADF handle was created for another number of atoms"};
+  }
+  void adf_sample_step(int64_t step, const double* pos, const PosQ* posq, const int* perm, int64_t n, const BoxD& box, const int* frozen)
+  {
+    for (AdfT<B>* r : adfs_)
+      if (r->sample_after(step))
+        r->sample(pos, posq, perm, n, box, frozen);
+  }
+  void adf_advance(int64_t nsteps)
+  {
+    for (AdfT<B>* r : adfs_)
+      r->advance(nsteps);
+  }
+  std::vector<AdfT<B>*> adfs_;
 
   template <class T>
   T* dalloc(size_t count)
@@ -2114,6 +2140,29 @@ public:
         return;
       }
     throw EngineError{-4, "rdf: not attached to this engine"};
+  }
+  // ADF handles (nep_adf.h): the rules of the RDF handles above; they sample after them
+  void adf_attach(AdfT<B>* r)
+  {
+    if (r->n() > cap_)
+      throw EngineError{-4, "adf: more atoms than the engine's capacity"};
+    for (AdfT<B>* o : adfs_)
+      if (o == r)
+        throw EngineError{-4, "adf: already attached"};
+    if (r->attached_to)
+      throw EngineError{-4, "adf: attached to another engine"};
+    adfs_.push_back(r);
+    r->attached_to = this;
+  }
+  void adf_detach(AdfT<B>* r)
+  {
+    for (size_t i = 0; i < adfs_.size(); ++i)
+      if (adfs_[i] == r) {
+        adfs_.erase(adfs_.begin() + i);
+        r->attached_to = nullptr;
+        return;
+      }
+    throw EngineError{-4, "adf: not attached to this engine"};
   }
   void check_flags_now()
   {

@@ -436,6 +436,8 @@ void Run::parse_one_keyword(const std::vector<std::string>& p)
     parse_compute_corr(p, false);
   } else if (k == "compute_rdf") {
     parse_compute_rdf(p);
+  } else if (k == "compute_adf") {
+    parse_compute_adf(p);
   } else if (k == "run") {
     if (p.size() != 2)
       input_error("run should have 1 parameter.");
@@ -455,6 +457,7 @@ void Run::parse_one_keyword(const std::vector<std::string>& p)
     msd_ = ComputeCorr();
     sdc_ = ComputeCorr();
     rdf_ = ComputeRdf();
+    adf_ = ComputeAdf();
   } else {
     input_error("'" + k + "' is invalid keyword (or outside the path gpumd-mi covers).");
   }
@@ -644,6 +647,180 @@ void Run::write_rdf()
   std::fclose(fid);
 }
 
+// ADF::parse (adf.cu:371-565), with its messages (the first one names compute_rdf there as well)
+void Run::parse_compute_adf(const std::vector<std::string>& p)
+{
+  std::printf("Compute angular distribution functions (ADF).\n");
+  if (adf_.active)
+    input_error("compute_adf can be used once in a run.");
+  ComputeAdf c;
+  c.active = true;
+  const int num_param = (int)p.size();
+  const int number_of_types = (int)elements.size();
+  if (num_param < 5)
+    input_error("compute_rdf should have at least 4 parameters.");
+  if (num_param != 5 && (num_param - 3) % 7 != 0)
+    input_error("compute_adf should have 4 parameters or 2 + 7 * Ntriples parameters.");
+  if (!is_valid_int(p[1], &c.interval))
+    input_error("interval step per sample should be an integer.");
+  if (c.interval <= 0)
+    input_error("interval step per sample should be positive.");
+  if (!is_valid_int(p[2], &c.num_bins))
+    input_error("number of bins should be an integer.");
+  double rc_max = 0.0;
+  if (num_param == 5) {
+    nepmi_adf_row r;
+    r.itype = r.jtype = r.ktype = -1;
+    if (!is_valid_real(p[3], &r.rmin_j))
+      input_error("minimum radial cutoff should be a number.");
+    if (!is_valid_real(p[4], &r.rmax_j))
+      input_error("maximum radial cutoff should be a number.");
+    if (r.rmin_j >= r.rmax_j)
+      input_error("minimum radial cutoff should be less than maximum radial cutoff.");
+    if (r.rmin_j < 0)
+      input_error("minimum radial cutoff should be positive.");
+    r.rmin_k = r.rmin_j;
+    r.rmax_k = r.rmax_j;
+    c.global = true;
+    c.rows.push_back(r);
+    rc_max = r.rmax_j;
+  } else {
+    const int num_triples = (num_param - 3) / 7;
+    if (num_triples > 32)
+      input_error("compute_adf takes at most 32 triples.");
+    for (int i = 0; i < num_triples; ++i) {
+      const std::string n = std::to_string(i);
+      nepmi_adf_row r;
+      int* types[3] = {&r.itype, &r.jtype, &r.ktype};
+      const char* names[3] = {"itype", "jtype", "ktype"};
+      for (int q = 0; q < 3; ++q) {
+        if (!is_valid_int(p[3 + q + i * 7], types[q]))
+          input_error(std::string(names[q]) + " in triples " + n + " should be an integer.");
+        if (*types[q] < 0)
+          input_error(std::string(names[q]) + " in triples " + n + " should be non-negative.");
+        if (*types[q] > number_of_types - 1)
+          input_error(std::string(names[q]) + " in triples " + n + " should be less than number of atomic types " +
+                      std::to_string(number_of_types) + ".");
+      }
+      double* lo[2] = {&r.rmin_j, &r.rmin_k};
+      double* hi[2] = {&r.rmax_j, &r.rmax_k};
+      for (int q = 0; q < 2; ++q) {
+        if (!is_valid_real(p[6 + 2 * q + i * 7], lo[q]))
+          input_error("minimum radial cutoff in triples " + n + " should be a number.");
+        if (!is_valid_real(p[7 + 2 * q + i * 7], hi[q]))
+          input_error("maximum radial cutoff in triples " + n + " should be a number.");
+        if (*lo[q] >= *hi[q])
+          input_error("minimum radial cutoff should be less than maximum radial cutoff for triples " + n + ".");
+        if (*lo[q] < 0)
+          input_error("minimum radial cutoff in triples " + n + " should be positive.");
+      }
+      c.rows.push_back(r);
+      rc_max = std::max(rc_max, std::max(r.rmax_j, r.rmax_k));
+    }
+    c.global = false;
+  }
+  {
+    const double* h = box.cpu_h; // columns a, b, c
+    const double a[3] = {h[0], h[3], h[6]}, b[3] = {h[1], h[4], h[7]}, cc[3] = {h[2], h[5], h[8]};
+    auto area = [](const double* u, const double* v) {
+      const double s1 = u[1] * v[2] - u[2] * v[1], s2 = u[2] * v[0] - u[0] * v[2], s3 = u[0] * v[1] - u[1] * v[0];
+      return std::sqrt(s1 * s1 + s2 * s2 + s3 * s3);
+    };
+    const double volume = box.get_volume();
+    const double thickness_half[3] = {volume / area(b, cc) / 2.5, volume / area(cc, a) / 2.5, volume / area(a, b) / 2.5};
+    if (rc_max > thickness_half[0] || rc_max > thickness_half[1] || rc_max > thickness_half[2])
+      input_error("The box has a thickness < 2.5 RDF radial cutoffs in a periodic direction.\n"
+                  "                Please increase the periodic direction(s).");
+  }
+  if (c.num_bins < 1 || c.num_bins > 4096) // (ours: the reference divides by zero bins and has no upper end)
+    input_error("number of bins should be 1 to 4096.");
+  if (c.global) {
+    std::printf("    Global ADF will be computed.\n");
+    std::printf("    ADF sample interval is %d step.\n", c.interval);
+    std::printf("    radial cutoff will be divided into %d bins.\n", c.num_bins);
+    std::printf("    minimal radial cutoff %g.\n", c.rows[0].rmin_j);
+    std::printf("    maximum radial cutoff %g.\n", c.rows[0].rmax_j);
+  } else {
+    std::printf("    Local triple ADF will be computed.\n");
+    std::printf("    ADF sample interval is %d step.\n", c.interval);
+    std::printf("    radial cutoff will be divided into %d bins.\n", c.num_bins);
+    for (const nepmi_adf_row& r : c.rows)
+      std::printf("    Triple %d-%d-%d: %g %g %g %g.\n", r.itype, r.jtype, r.ktype, r.rmin_j, r.rmax_j, r.rmin_k, r.rmax_k);
+  }
+  adf_ = c;
+}
+
+// ADF::preprocess (adf.cu:183-235): the handle of this run, attached to the engine
+void Run::adf_open()
+{
+  if (!adf_.active)
+    return;
+  nepmi_engine* e = force.engine();
+  die_on(nepmi_adf_create(e, atom.number_of_atoms, adf_.num_bins, adf_.interval, adf_.rows.data(), (int)adf_.rows.size(),
+                          atom.cpu_type.data(), (int)elements.size(), &adf_.handle), "ADF");
+  die_on(nepmi_adf_attach(e, adf_.handle), "ADF");
+}
+
+void Run::adf_close()
+{
+  if (adf_.handle) {
+    die_on(nepmi_adf_detach(force.engine(), adf_.handle), "adf_detach");
+    nepmi_adf_destroy(adf_.handle);
+    adf_.handle = nullptr;
+  }
+}
+
+// the output half of ADF::process (adf.cu:312-350): one block of the CUMULATIVE counts, appended
+void Run::write_adf(int step)
+{
+  const ComputeAdf& c = adf_;
+  const int M = (int)c.rows.size(), nb = c.num_bins;
+  std::vector<uint64_t> counts((size_t)M * nb);
+  int64_t samples = 0;
+  const int st = nepmi_adf_read(c.handle, counts.data(), &samples);
+  if (st == NEPMI_ERR_CAPACITY) {
+    std::printf("compute_adf: an atom has more than %d neighbours within the radial cutoffs; the run ends here.\n    (%s)\n",
+                nepmi_adf_capacity(), nepmi_last_error());
+    std::fflush(stdout);
+    std::exit(1);
+  }
+  die_on(st, "adf_read");
+  FILE* fid = std::fopen("adf.out", "a");
+  if (!fid)
+    input_error("Cannot open adf.out for writing.");
+  const double delta_theta = 180.0 / nb;
+  std::vector<double> angle((size_t)nb);
+  for (int i = 1; i < nb + 1; ++i)
+    angle[(size_t)i - 1] = (i * delta_theta + (i - 1) * delta_theta) / 2;
+  const double delta = nb > 1 ? angle[1] - angle[0] : delta_theta;
+  std::fprintf(fid, "#angles ");
+  if (c.global) {
+    std::fprintf(fid, "total step = %d\n", step);
+  } else {
+    for (const nepmi_adf_row& r : c.rows)
+      std::fprintf(fid, "triples_%d-%d-%d ", r.itype, r.jtype, r.ktype);
+    std::fprintf(fid, "step = %d\n", step);
+  }
+  std::vector<double> total((size_t)M, 0.0);
+  for (int m = 0; m < M; ++m) {
+    uint64_t t = 0;
+    for (int i = 0; i < nb; ++i)
+      t += counts[(size_t)m * nb + i];
+    total[(size_t)m] = (double)t;
+  }
+  for (int i = 0; i < nb; ++i) {
+    std::fprintf(fid, "%g ", angle[(size_t)i]);
+    for (int m = 0; m < M; ++m) {
+      const double v = (double)counts[(size_t)m * nb + i];
+      const double x = total[(size_t)m] > 0 ? v / (total[(size_t)m] * delta * 1.0) : v / (delta * 1.0);
+      std::fprintf(fid, c.global ? "%g" : "%g ", x);
+    }
+    std::fprintf(fid, "\n");
+  }
+  std::fflush(fid);
+  std::fclose(fid);
+}
+
 // MSD::preprocess (msd.cu:205-267) / SDC::preprocess (sdc.cu:132-155): the correlator of this run, attached to the engine
 void Run::corr_open(ComputeCorr& c, int quantity, const char* name)
 {
@@ -698,6 +875,12 @@ void Run::corr_sample_stepwise()
   if (rdf_.handle && corr_steps_ % rdf_.interval == 0) {
     const int pbc[3] = {box.pbc_x, box.pbc_y, box.pbc_z};
     die_on(nepmi_rdf_sample(rdf_.handle, atom.position_per_atom.data(), box.cpu_h, pbc), "rdf_sample");
+  }
+  if (adf_.handle && corr_steps_ % adf_.interval == 0) {
+    const int pbc[3] = {box.pbc_x, box.pbc_y, box.pbc_z};
+    const int st = nepmi_adf_sample(adf_.handle, atom.position_per_atom.data(), box.cpu_h, pbc);
+    if (st != NEPMI_ERR_CAPACITY) // (write_adf reports an overflowed handle at the end of the segment)
+      die_on(st, "adf_sample");
   }
 }
 
@@ -1284,6 +1467,7 @@ void Run::perform_a_run()
   corr_open(msd_, 0, "MSD");
   corr_open(sdc_, 1, "SDC");
   rdf_open();
+  adf_open();
   // target temperature of a temperature-dependent NEP (Run::parse_run, run.cu:679-681)
   // (integrate.temperature1/2 keep the values of the last ensemble that had them; an NVE-only input leaves them
   // uninitialised in the reference -- here they start at 300 K)
@@ -1333,6 +1517,8 @@ void Run::perform_a_run()
       upto(active_.interval);
     if (msd_.active)
       upto(msd_.save_every); // msd_step<k>.out
+    if (adf_.active)
+      upto(adf_.interval); // a block of adf.out
     if (number_of_steps >= 10)
       upto(number_of_steps / 10); // progress lines
     if (correct_interval_ > 0) { // the correction precedes the steps 0, k, 2k, ...: a segment ends right before them
@@ -1361,6 +1547,8 @@ void Run::perform_a_run()
     if (msd_.handle && msd_.save_every > 0 && done % msd_.save_every == 0 && done % msd_.interval == 0 &&
         step / msd_.interval >= msd_.num_corr - 1)
       write_msd(("msd_step" + std::to_string(done) + ".out").c_str());
+    if (adf_.handle && done % adf_.interval == 0)
+      write_adf(step); // ADF::process
     if (number_of_steps >= 10 && (step + 1) % (number_of_steps / 10) == 0)
       std::printf("    %d steps completed.\n", step + 1);
   }
@@ -1376,6 +1564,7 @@ void Run::perform_a_run()
   corr_close(msd_);
   corr_close(sdc_);
   rdf_close();
+  adf_close();
   const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   std::printf("Time used for this run = %g second.\n", sec);
   std::printf("Speed of this run = %g atom*step/second.\n", (double)N * number_of_steps / sec); // run.cu:325-326
@@ -1521,6 +1710,8 @@ void Run::perform_a_run_dist()
     input_error("compute_sdc is not available in multi-GPU runs.");
   if (rdf_.active)
     input_error("compute_rdf is not available in multi-GPU runs.");
+  if (adf_.active)
+    input_error("compute_adf is not available in multi-GPU runs.");
   const int N = atom.number_of_atoms;
   const bool root = par_.rank == 0;
   const int ens = ensemble == "nve" ? 0 : ensemble == "nvt_ber" ? 1 : ensemble == "nvt_nhc" ? 2 : ensemble == "nvt_bdp" ? 3

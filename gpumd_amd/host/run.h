@@ -64,6 +64,17 @@ struct ComputeRdf {
   nepmi_rdf* handle = nullptr;       // of the run in progress
 };
 
+// ADF (src/measure/adf.cuh): `compute_adf <interval> <num_bins> <rc_min> <rc_max>` or `compute_adf <interval> <num_bins>
+// (<itype> <jtype> <ktype> <rc_min_j> <rc_max_j> <rc_min_k> <rc_max_k>)+`.  The triplet counts are libnepmi's (nepmi_adf_*),
+// sampled inside the run loops; the run is cut at the sample steps, where the host appends a block to adf.out.
+struct ComputeAdf {
+  bool active = false;
+  bool global = true;
+  int interval = 0, num_bins = 0;
+  std::vector<nepmi_adf_row> rows;
+  nepmi_adf* handle = nullptr;       // of the run in progress
+};
+
 // One process per GPU (torchrun / mpirun style launch: RANK, WORLD_SIZE, LOCAL_RANK, MASTER_ADDR, MASTER_PORT or
 // OMPI_COMM_WORLD_*): the run is domain-decomposed by libnepmi's nepmi_dist_* driver (RCCL over xGMI when every
 // rank has its own GPU, TCP sockets otherwise); rank 0 writes the output files.
@@ -110,6 +121,10 @@ private:
   void rdf_open();
   void rdf_close();
   void write_rdf();
+  void parse_compute_adf(const std::vector<std::string>& p);
+  void adf_open();
+  void adf_close();
+  void write_adf(int step);
 
   bool check_only_;
   Parallel par_;
@@ -143,6 +158,7 @@ private:
   ActiveLearning active_;
   ComputeCorr msd_, sdc_;
   ComputeRdf rdf_;
+  ComputeAdf adf_;
   int corr_steps_ = 0; // finished steps of the run in progress (the paths that step by hand sample on it)
   GPU_Vector<double> thermo; // 8 doubles
   std::vector<std::string> elements;

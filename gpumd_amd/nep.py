@@ -138,14 +138,18 @@ class NEP:
         self._ck(self.lib.nepmi_engine_set_unwrapped(self.handle, self._ptr(unwrapped) if unwrapped is not None else None))
 
     def attach(self, corr):
-        """The run_* methods sample `corr` (a Correlator or an RDF of this engine) every corr.interval completed steps."""
-        if isinstance(corr, RDF):
+        """The run_* methods sample `corr` (a Correlator, an RDF or an ADF of this engine) every corr.interval completed steps."""
+        if isinstance(corr, ADF):
+            self._ck(self.lib.nepmi_adf_attach(self.handle, corr.handle))
+        elif isinstance(corr, RDF):
             self._ck(self.lib.nepmi_rdf_attach(self.handle, corr.handle))
         else:
             self._ck(self.lib.nepmi_corr_attach(self.handle, corr.handle))
 
     def detach(self, corr):
-        if isinstance(corr, RDF):
+        if isinstance(corr, ADF):
+            self._ck(self.lib.nepmi_adf_detach(self.handle, corr.handle))
+        elif isinstance(corr, RDF):
             self._ck(self.lib.nepmi_rdf_detach(self.handle, corr.handle))
         else:
             self._ck(self.lib.nepmi_corr_detach(self.handle, corr.handle))
@@ -567,6 +571,96 @@ class RDF:
 
     def __del__(self):
         self.close()
+
+
+class AdfRow(C.Structure):
+    _fields_ = [("itype", C.c_int), ("jtype", C.c_int), ("ktype", C.c_int),
+                ("rmin_j", C.c_double), ("rmax_j", C.c_double), ("rmin_k", C.c_double), ("rmax_k", C.c_double)]
+
+
+class ADF:
+    """Angular distribution function as integer triplet counts (nepmi_adf_*): `num_bins` bins over 0 .. 180 degrees, one row of
+    counts per entry of `rows`.  A row is (itype, jtype, ktype, rmin_j, rmax_j, rmin_k, rmax_k) with the types all -1 (any) or all
+    >= 0; (rmin, rmax) alone is the global form: any types, both ranges equal.  `type_of_atom`: n ints in the caller's atom
+    order, 0 .. num_types - 1; not needed when every row is "any".
+
+    Attach it to the engine (`engine.attach(a)`) and the run_* methods sample it on the device every `interval` steps; a host
+    that steps by hand calls `sample(pos, h, pbc)` with pos = [3N] f64 on the device.  `read()` -> (counts [M, num_bins] uint64,
+    cumulative over the samples, num_samples); `density()` normalises as the reference's adf.out.  A centre atom with more than
+    `capacity` neighbours in range voids the sample: `sample` and every later `read` raise with code -6.
+    `lds_budget` (bytes) moves the threshold between the two forms of the triplet kernel; `form` is 1 (tables in LDS) or 2."""
+
+    def __init__(self, engine, rows, num_bins, interval, type_of_atom=None, num_types=0, lds_budget=None):
+        self.engine = engine
+        self.lib = engine.lib
+        self.num_bins, self.interval, self.num_types = int(num_bins), int(interval), int(num_types)
+        rows = list(rows)
+        if len(rows) == 2 and not hasattr(rows[0], "__len__"):
+            rows = [(-1, -1, -1, rows[0], rows[1], rows[0], rows[1])]
+        self.rows = [tuple(r) for r in rows]
+        self.num_rows = len(self.rows)
+        arr = (AdfRow * max(1, self.num_rows))()
+        for m, r in enumerate(self.rows):
+            arr[m] = AdfRow(int(r[0]), int(r[1]), int(r[2]), float(r[3]), float(r[4]), float(r[5]), float(r[6]))
+        tp = None
+        if type_of_atom is not None:
+            t = np.ascontiguousarray(np.asarray(type_of_atom), dtype=np.int32)
+            if t.shape != (engine.n,):
+                raise ValueError("type_of_atom: one int per atom")
+            tp = t.ctypes.data_as(_capi.c_ip)
+        out = C.c_void_p()
+        _capi.check(self.lib, self.lib.nepmi_adf_create(engine.handle, engine.n, self.num_bins, self.interval,
+                                                        C.cast(arr, C.c_void_p), self.num_rows, tp, self.num_types, C.byref(out)))
+        self.handle = out
+        if not hasattr(engine, "_correlators"):
+            engine._correlators = weakref.WeakSet()
+        engine._correlators.add(self)
+        if lds_budget is not None:
+            _capi.check(self.lib, self.lib.nepmi_adf_set_lds_budget(self.handle, int(lds_budget)))
+
+    @property
+    def form(self):
+        return _capi.check(self.lib, self.lib.nepmi_adf_form(self.handle))
+
+    @property
+    def capacity(self):
+        return int(self.lib.nepmi_adf_capacity())
+
+    def sample(self, pos, h, pbc):
+        _, hp = _h9(h)
+        _, pp = _pbc3(pbc)
+        _capi.check(self.lib, self.lib.nepmi_adf_sample(self.handle, NEP._ptr(pos), hp, pp))
+
+    def read(self):
+        counts = np.zeros((self.num_rows, self.num_bins), dtype=np.uint64)
+        ns = C.c_int64(0)
+        _capi.check(self.lib, self.lib.nepmi_adf_read(self.handle, counts.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(ns)))
+        return counts, int(ns.value)
+
+    def density(self):
+        """-> (angle [num_bins] in degrees, the bin centres; density [M, num_bins]): adf.cu:315-350 on the integer sums"""
+        counts, _ = self.read()
+        return adf_normalise(counts)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.nepmi_adf_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        self.close()
+
+
+def adf_normalise(counts):
+    """The one normalisation of the ADF sums: every row divided by its own total x the bin width in degrees, or by the bin width
+    alone when the total is 0; the angles are the bin centres."""
+    counts = np.asarray(counts)
+    nb = counts.shape[1]
+    edges = np.arange(nb + 1) * (180.0 / nb)
+    angle = (edges[1:] + edges[:-1]) / 2
+    delta = angle[1] - angle[0] if nb > 1 else 180.0
+    total = counts.sum(axis=1, dtype=np.uint64).astype(np.float64)
+    return angle, counts.astype(np.float64) / (np.where(total > 0, total, 1.0) * delta)[:, None]
 
 
 def rdf_normalise(vsum, rc, num_atoms_of_type, num_repeats):

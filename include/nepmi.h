@@ -180,6 +180,45 @@ int nepmi_rdf_detach(nepmi_engine* e, nepmi_rdf* rdf);
 int nepmi_rdf_read(nepmi_rdf* rdf, uint64_t* counts_host, double* vsum_host, int64_t* num_samples);
 int nepmi_rdf_set_lds_budget(nepmi_rdf* rdf, int64_t bytes);
 int nepmi_rdf_form(nepmi_rdf* rdf);
+/* ---- Angular distribution function sampled while the engine runs (replaces ADF::process / gpu_find_adf_global / _local,
+ *      src/measure/adf.cu:37-176, :237-310; the normalisation and the output, adf.cu:315-350, belong to the reader).
+ * A handle holds num_rows rows (1 .. 32) and num_bins bins (1 .. 4096).  A row is (itype, jtype, ktype, [rmin_j, rmax_j),
+ * [rmin_k, rmax_k)); its types are all -1 ("any": the global form of compute_adf is one such row with both ranges equal) or
+ * all >= 0.  For a centre atom i, a neighbour a != i at the minimum-image distance d (apply_mic, double) is in role J of the
+ * row if its type matches jtype and rmin_j^2 <= d^2 < rmax_j^2 (closed below, open above, adf.cu:75, :143), in role K likewise.
+ * The row counts the unordered pair {a, b} once for the centre i if type(i) matches itype and (J(a) and K(b)) or (J(b) and
+ * K(a)), in the bin min(floor(theta / (180 / num_bins)), num_bins - 1) of theta = acos(c) 180 / pi, c the cosine at i clamped
+ * to [-1, 1].  This is the reference's count except that (1) for jtype == ktype with different ranges the reference's count
+ * depends on the order of its neighbour list and this one does not, (2) a neighbour at d = 0 is never a member, (3) there is
+ * no list of 200 neighbours cut in float, (4) the clamp.  The object owns, on the device,
+ *   counts [num_rows][num_bins] unsigned 64-bit, CUMULATIVE over the samples (as the reference prints them),
+ * and the sample counter; nothing in floating point.
+ * type_of_atom: HOST array of n ints in the caller's atom order, 0 .. num_types - 1; may be NULL when every row is "any".
+ *   _sample / _attach / _detach / _set_lds_budget / _form: as nepmi_rdf_*; an attached handle samples after the RDF handles.
+ *   _read:     counts_host (HOST, [num_rows][num_bins], may be NULL) and the samples so far.
+ *   _capacity: the members (neighbours in role J or K of some row) one centre atom may have.  A sample in which a centre has
+ *              more adds NOTHING to the counts, nepmi_adf_sample returns NEPMI_ERR_CAPACITY and so does every later
+ *              nepmi_adf_read: never a silent undercount.
+ * Errors (NEPMI_ERR_ARG): n is not the engine's, num_bins outside 1 .. 4096, num_rows outside 1 .. 32, rmin < 0 or rmin >= rmax,
+ * a type outside range, the largest rmax above thickness / 2.5 of the sample's box in any direction (adf.cu:404-413, asked at
+ * EVERY sample), a handle attached twice or to another engine.
+ * Lifetime: as nepmi_rdf -- destroy it BEFORE the engine it was created from. ---- */
+typedef struct nepmi_adf nepmi_adf;
+typedef struct {
+  int itype, jtype, ktype;
+  double rmin_j, rmax_j, rmin_k, rmax_k;
+} nepmi_adf_row;
+int nepmi_adf_create(
+  nepmi_engine* e, int64_t n, int num_bins, int64_t sample_interval, const nepmi_adf_row* rows, int num_rows,
+  const int* type_of_atom, int num_types, nepmi_adf** out);
+void nepmi_adf_destroy(nepmi_adf* adf);
+int nepmi_adf_sample(nepmi_adf* adf, const double* pos, const double* h9, const int* pbc3);
+int nepmi_adf_attach(nepmi_engine* e, nepmi_adf* adf);
+int nepmi_adf_detach(nepmi_engine* e, nepmi_adf* adf);
+int nepmi_adf_read(nepmi_adf* adf, uint64_t* counts_host, int64_t* num_samples);
+int nepmi_adf_set_lds_budget(nepmi_adf* adf, int64_t bytes);
+int nepmi_adf_form(nepmi_adf* adf);
+int nepmi_adf_capacity(void);
 /* The same call in two halves, so that a domain-decomposed host can overlap its ghost-position
  * exchange (the RCCL send/recv that replaces NEP_MULTIGPU's staged copies) with compute:
  *   _begin: the OWNED (level 2) entries of pos are final; ghost entries may still be in flight and
