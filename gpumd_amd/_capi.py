@@ -123,6 +123,8 @@ SYMBOLS = {
     "nepmi_corr_attach": (C.c_int, [VP, VP]),
     "nepmi_corr_detach": (C.c_int, [VP, VP]),
     "nepmi_corr_read": (C.c_int, [VP, c_dp, C.POINTER(c_i64), C.POINTER(c_i64)]),
+    "nepmi_corr_create_weighted": (C.c_int, [VP, C.c_int, c_i64, c_i64, C.c_int, c_ip, C.c_int, c_dp, C.POINTER(VP)]),
+    "nepmi_dos_from_mvac": (C.c_int, [c_dp, C.c_int, C.c_int, C.POINTER(c_i64), C.c_double, C.c_double, C.c_int, c_dp, c_dp]),
     "nepmi_rdf_create": (C.c_int, [VP, c_i64, C.c_double, C.c_int, c_i64, c_ip, C.c_int, C.POINTER(VP)]),
     "nepmi_rdf_destroy": (None, [VP]),
     "nepmi_rdf_sample": (C.c_int, [VP, VP, c_dp, c_ip]),

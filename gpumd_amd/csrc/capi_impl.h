@@ -639,12 +639,11 @@ int nepmi_engine_set_unwrapped(nepmi_engine* e, double* d_unwrapped)
   return NEPMI_OK;
 }
 
-int nepmi_corr_create(
+namespace {
+int corr_create_common(
   nepmi_engine* e, int quantity, int64_t n, int64_t sample_interval, int num_corr, const int* group_of_atom, int num_groups,
-  nepmi_corr** out)
+  const double* weight_host, nepmi_corr** out)
 {
-  if (!e || !out)
-    return fail(NEPMI_ERR_ARG, "null argument");
   *out = nullptr;
   nepmi_corr* c = new nepmi_corr();
   c->api = NEPMI_SELF_API;
@@ -652,13 +651,81 @@ int nepmi_corr_create(
   const int st = guarded([&] {
     if (n != e->e->num_atoms())
       throw nepmi::EngineError{NEPMI_ERR_ARG, "correlator: n is not the engine's number of atoms"};
-    c->c = new nepmi::CorrelatorT<NepmiBackend>(e->e->backend(), quantity, n, sample_interval, num_corr, group_of_atom, num_groups);
+    c->c = new nepmi::CorrelatorT<NepmiBackend>(e->e->backend(), quantity, n, sample_interval, num_corr, group_of_atom, num_groups,
+                                                weight_host);
   });
   if (st != NEPMI_OK) {
     delete c;
     return st;
   }
   *out = c;
+  return NEPMI_OK;
+}
+} // namespace
+
+int nepmi_corr_create(
+  nepmi_engine* e, int quantity, int64_t n, int64_t sample_interval, int num_corr, const int* group_of_atom, int num_groups,
+  nepmi_corr** out)
+{
+  if (!e || !out)
+    return fail(NEPMI_ERR_ARG, "null argument");
+  return corr_create_common(e, quantity, n, sample_interval, num_corr, group_of_atom, num_groups, nullptr, out);
+}
+
+int nepmi_corr_create_weighted(
+  nepmi_engine* e, int quantity, int64_t n, int64_t sample_interval, int num_corr, const int* group_of_atom, int num_groups,
+  const double* weight_host, nepmi_corr** out)
+{
+  if (!e || !out)
+    return fail(NEPMI_ERR_ARG, "null argument");
+  *out = nullptr;
+  if (quantity == 0 || quantity == 1)
+    return fail(NEPMI_ERR_ARG, "correlator: weights belong to quantity 2 (MVAC)");
+  if (quantity != 2)
+    return fail(NEPMI_ERR_ARG, "correlator: the weighted quantity should be 2 (MVAC)");
+  if (!weight_host)
+    return fail(NEPMI_ERR_ARG, "correlator: quantity 2 (MVAC) needs the weight array");
+  return corr_create_common(e, quantity, n, sample_interval, num_corr, group_of_atom, num_groups, weight_host, out);
+}
+
+// normalize_vac and find_dos, src/measure/dos.cu:414-427 and 450-481 (host only)
+int nepmi_dos_from_mvac(
+  const double* sums, int num_groups, int num_corr, const int64_t* group_size, double dt_ps, double omega_max, int num_dos_points,
+  double* mvac_out, double* dos_out)
+{
+  if (!sums || !group_size || !mvac_out || !dos_out)
+    return fail(NEPMI_ERR_ARG, "null argument");
+  if (num_groups < 1 || num_corr < 1 || num_dos_points < 1)
+    return fail(NEPMI_ERR_ARG, "dos: number of groups, of correlation steps and of DOS points should be positive");
+  if (!(dt_ps > 0.0) || !(omega_max > 0.0))
+    return fail(NEPMI_ERR_ARG, "dos: sampling time and maximal angular frequency should be positive");
+  const double pi = 3.14159265358979323846;
+  const double d_omega = omega_max / num_dos_points;
+  std::vector<double> windowed((size_t)num_corr);
+  for (int g = 0; g < num_groups; ++g)
+    for (int d = 0; d < 3; ++d) {
+      const double* s = sums + ((size_t)g * 3 + d) * num_corr;
+      double* mvac = mvac_out + ((size_t)g * 3 + d) * num_corr;
+      double* dos = dos_out + ((size_t)g * 3 + d) * num_dos_points;
+      const double s0 = s[0];
+      if (s0 == 0.0) { // an empty group (the reference prints 0 / 0 there)
+        std::fill(mvac, mvac + num_corr, 0.0);
+        std::fill(dos, dos + num_dos_points, 0.0);
+        continue;
+      }
+      for (int l = 0; l < num_corr; ++l) {
+        mvac[l] = s[l] / s0;
+        const double hann = (std::cos((pi * l) / num_corr) + 1.0) * 0.5;
+        windowed[l] = mvac[l] * (l == 0 ? hann : 2.0 * hann);
+      }
+      for (int k = 0; k < num_dos_points; ++k) {
+        const double omega = d_omega + k * d_omega;
+        double sum = 0.0;
+        for (int l = 0; l < num_corr; ++l)
+          sum += windowed[l] * std::cos(omega * l * dt_ps);
+        dos[k] = sum * (dt_ps * 2.0 * (double)group_size[g]);
+      }
+    }
   return NEPMI_OK;
 }
 

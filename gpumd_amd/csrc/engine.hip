@@ -1213,6 +1213,8 @@ struct HipBackend {
     if (grid > 0) {
       if (a.quantity == 0)
         hipLaunchKernelGGL((nepmi_corr_tiles<0>), dim3((unsigned)grid), dim3(256), 0, stream, a, frozen);
+      else if (a.quantity == 2)
+        hipLaunchKernelGGL((nepmi_corr_tiles<2>), dim3((unsigned)grid), dim3(256), 0, stream, a, frozen);
       else
         hipLaunchKernelGGL((nepmi_corr_tiles<1>), dim3((unsigned)grid), dim3(256), 0, stream, a, frozen);
       NEPMI_HIP_CHECK(hipGetLastError());

@@ -1214,10 +1214,10 @@ private:
         throw EngineError{-4, "an MSD correlator is attached but the unwrapped positions are switched off"};
     }
   }
-  bool corr_vac_step(int64_t step) const // a VAC sample reads the velocities behind this step: its second half-kick cannot wait
+  bool corr_vac_step(int64_t step) const // a VAC or MVAC sample reads the velocities behind this step: its second half-kick cannot wait
   {
     for (const CorrelatorT<B>* c : corrs_)
-      if (c->quantity() == 1 && c->sample_index_after(step) >= 0)
+      if (c->samples_velocities() && c->sample_index_after(step) >= 0)
         return true;
     return false;
   }

@@ -1,9 +1,15 @@
 // Time-correlation sums of per-atom vectors, sampled while a run loop owns the state (nepmi_corr_*, include/nepmi.h):
 //   quantity 0 (MSD): sum_i (u_i(t) - u_i(t - l))^2 per component, on unwrapped positions  -- MSD::process, src/measure/msd.cu:269-362
 //   quantity 1 (VAC): sum_i  v_i(t) * v_i(t - l)    per component                         -- SDC::process, src/measure/sdc.cu:157-224
+//   quantity 2 (MVAC): sum_i (w_i * v_i(t)) * v_i(t - l) per component, w_i a weight per atom (the mass)
+//                                                                                        -- gpu_find_vac, src/measure/dos.cu:84-143
 // with the reference's bookkeeping: sample s goes to slot s % num_corr of a ring of frames, and from s >= num_corr - 1 on every
 // sample is a time origin that adds, for each lag l, the current frame against the one in slot (s - l) mod num_corr.  The
 // normalisation (1 / (atoms * origins)) is the reader's.
+//
+// The weights of quantity 2 are kept in the ring's order, zero in the gaps, and are multiplied into the current frame once per
+// sample -- not per lag -- so the walk over the lags is that of quantity 1.  nepmi_dos_from_mvac (capi_impl.h) turns the sums into
+// the normalised MVAC and the density of states.
 //
 // The ring keeps its OWN atom order -- sorted by group, then by the caller's index, every group starting at an even index (the gap
 // is a slot nobody writes: zero in every frame, so it adds (0 - 0)^2 or 0 * 0) -- so that
@@ -50,6 +56,7 @@ struct CorrArgs {
   int lag_chunk, num_chunks;
   double* partial; // [num_corr * 3][num_tiles]
   double* acc;     // [num_groups][3][num_corr]
+  const double* weight; // [ns], quantity 2 only: the per-atom weights in the ring's order, zero in the gaps
 };
 
 // frame[d][order_of[i]] = q[d][k], i = perm[k] (internal order) or k (caller's order, perm == nullptr)
@@ -92,6 +99,8 @@ struct CorrPlainBody {
         if (a.quantity == 0) {
           const double dx = c[j] - o[j];
           s += dx * dx;
+        } else if (a.quantity == 2) {
+          s += (a.weight[j] * c[j]) * o[j];
         } else {
           s += c[j] * o[j];
         }
@@ -129,6 +138,14 @@ __global__ void __launch_bounds__(256) nepmi_corr_tiles(const CorrArgs a, const 
 #pragma unroll
     for (int d = 0; d < 3; ++d)
       c[d] = *reinterpret_cast<const double2*>(a.ring + ((int64_t)a.cur * 3 + d) * a.ns + j);
+    if (Q == 2) { // the weights go into the current frame: once per sample, and the lags below are those of Q == 1
+      const double2 w = *reinterpret_cast<const double2*>(a.weight + j);
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        c[d].x *= w.x;
+        c[d].y *= w.y;
+      }
+    }
   }
   const int l0 = chunk * a.lag_chunk;
   const int l1 = l0 + a.lag_chunk < a.num_corr ? l0 + a.lag_chunk : a.num_corr;
@@ -194,12 +211,16 @@ class CorrelatorT
 public:
   static constexpr int kTargetWorkgroups = 1024; // 4 per CU of the 256: 13,824 atoms x 100 lags are 27 tiles x 34 chunks, not 27 workgroups
 
-  CorrelatorT(const B& be, int quantity, int64_t n, int64_t interval, int num_corr, const int* group_of_atom, int num_groups)
+  // weight: HOST [n] in the caller's order, for quantity 2 and for it only (nepmi_corr_create_weighted)
+  CorrelatorT(const B& be, int quantity, int64_t n, int64_t interval, int num_corr, const int* group_of_atom, int num_groups,
+              const double* weight = nullptr)
     : be_(be), quantity_(quantity), n_(n), interval_(interval), num_corr_(num_corr), num_groups_(num_groups)
   {
     be_.frozen = nullptr;
-    if (quantity != 0 && quantity != 1)
+    if (!weight && quantity != 0 && quantity != 1)
       throw EngineError{-4, "correlator: quantity should be 0 (MSD) or 1 (VAC)"};
+    if (weight && quantity != 2)
+      throw EngineError{-4, "correlator: weights belong to quantity 2 (MVAC)"};
     if (n < 1 || n > 2000000000)
       throw EngineError{-4, "correlator: bad number of atoms"};
     if (interval < 1 || num_corr < 1 || num_groups < 1)
@@ -237,6 +258,16 @@ public:
     }
     tile_first[num_groups] = (int)tiles.size();
     num_tiles_ = (int)tiles.size();
+    std::vector<double> w_ring;
+    if (weight) {
+      w_ring.assign((size_t)std::max<int64_t>(ns_, 2), 0.0); // (the gaps: zero)
+      for (int64_t i = 0; i < n; ++i) {
+        if (!(weight[i] >= 0.0) || !(weight[i] <= 1.7976931348623157e308)) // (NaN fails both)
+          throw EngineError{-4, "correlator: weight should be finite and not negative"};
+        if (order[i] >= 0)
+          w_ring[(size_t)order[i]] = weight[i];
+      }
+    }
     // lags per workgroup: all of them where the tiles alone fill the device, fewer where they do not
     int chunks = num_tiles_ > 0 ? (kTargetWorkgroups + num_tiles_ - 1) / num_tiles_ : 1;
     chunks = std::max(chunks, (num_corr + kCorrMaxLagChunk - 1) / kCorrMaxLagChunk);
@@ -257,6 +288,10 @@ public:
       if (!tiles.empty())
         be_.h2d(tiles_, tiles.data(), sizeof(CorrTile) * tiles.size());
       be_.h2d(tile_first_, tile_first.data(), sizeof(int) * tile_first.size());
+      if (weight) {
+        weight_ = (double*)dalloc(sizeof(double) * w_ring.size());
+        be_.h2d(weight_, w_ring.data(), sizeof(double) * w_ring.size());
+      }
     } catch (...) {
       release();
       throw;
@@ -268,6 +303,7 @@ public:
 
   void* attached_to = nullptr; // the engine whose run loops sample this correlator (EngineT::corr_attach)
   int quantity() const { return quantity_; }
+  bool samples_velocities() const { return quantity_ != 0; } // VAC and MVAC: the second half-kick of a sample step cannot wait
   int64_t n() const { return n_; }
   int64_t num_samples() const { return num_samples_; }
   int64_t num_origins() const { return std::max<int64_t>(0, num_samples_ - (num_corr_ - 1)); }
@@ -300,7 +336,7 @@ public:
       be_.template launch<256>(kSlotMisc, N, CorrGatherBody{q, N, perm, order_of_, ring_ + (int64_t)cur * 3 * ns_, ns_});
       if (s >= num_corr_ - 1) {
         const CorrArgs a{ring_, ns_, num_corr_, cur, quantity_, tiles_, tile_first_, num_tiles_, num_groups_, lag_chunk_, num_chunks_,
-                         partial_, acc_};
+                         partial_, acc_, weight_};
         if constexpr (BackendHasCorr<B>::value)
           be_.launch_corr(a);
         else
@@ -358,6 +394,7 @@ private:
   double* ring_ = nullptr;
   double* acc_ = nullptr;
   double* partial_ = nullptr;
+  double* weight_ = nullptr;
   int* order_of_ = nullptr;
   CorrTile* tiles_ = nullptr;
   int* tile_first_ = nullptr;

@@ -434,6 +434,8 @@ void Run::parse_one_keyword(const std::vector<std::string>& p)
     parse_compute_corr(p, true);
   } else if (k == "compute_sdc") {
     parse_compute_corr(p, false);
+  } else if (k == "compute_dos") {
+    parse_compute_dos(p);
   } else if (k == "compute_rdf") {
     parse_compute_rdf(p);
   } else if (k == "compute_adf") {
@@ -456,6 +458,7 @@ void Run::parse_one_keyword(const std::vector<std::string>& p)
     active_.active = false;
     msd_ = ComputeCorr();
     sdc_ = ComputeCorr();
+    dos_ = ComputeCorr();
     rdf_ = ComputeRdf();
     adf_ = ComputeAdf();
   } else {
@@ -522,6 +525,64 @@ void Run::parse_compute_corr(const std::vector<std::string>& p, bool msd)
   if (c.all_groups && c.grouping_method >= 0 && c.group_id >= 0)
     input_error("Cannot compute MSD over a single group and all groups at the same time");
   (msd ? msd_ : sdc_) = c;
+}
+
+// DOS::parse (dos.cu:153-202) and parse_num_dos_points (dos.cu:270-279), with their messages; parse_group with all groups allowed
+void Run::parse_compute_dos(const std::vector<std::string>& p)
+{
+  std::printf("Compute phonon DOS.\n");
+  ComputeCorr c;
+  c.active = true;
+  if (p.size() < 4)
+    input_error("compute_dos should have at least 3 parameters.");
+  if (p.size() > 9)
+    input_error("compute_dos has too many parameters.");
+  if (!is_valid_int(p[1], &c.interval))
+    input_error("sample interval should be an integer.");
+  if (c.interval <= 0)
+    input_error("sample interval should be positive.");
+  std::printf("    sample interval is %d.\n", c.interval);
+  if (!is_valid_int(p[2], &c.num_corr))
+    input_error("number of correlation steps should be an integer.");
+  if (c.num_corr <= 0)
+    input_error("number of correlation steps should be positive.");
+  std::printf("    number of correlation steps is %d.\n", c.num_corr);
+  if (!is_valid_real(p[3], &c.omega_max))
+    input_error("maximal angular frequency should be a number.");
+  if (c.omega_max <= 0)
+    input_error("maximal angular frequency should be positive.");
+  std::printf("    maximal angular frequency is %g THz.\n", c.omega_max);
+  for (size_t m = 4; m < p.size(); ++m) {
+    if (p[m] == "group") { // parse_group, parse_utilities.cu:27-64
+      if (m + 3 > p.size())
+        input_error("Not enough arguments for option 'group'.");
+      if (!is_valid_int(p[m + 1], &c.grouping_method))
+        input_error("Grouping method should be an integer.");
+      if (c.grouping_method < 0)
+        input_error("Grouping method should >= 0.");
+      if (c.grouping_method >= (int)groups.size())
+        input_error("Grouping method should < number of grouping methods.");
+      if (!is_valid_int(p[m + 2], &c.group_id))
+        input_error("Group ID should be an integer.");
+      if (c.group_id >= groups[c.grouping_method].number)
+        input_error("Group ID should < number of groups.");
+      std::printf("    grouping method is %d and group ID is %d.\n", c.grouping_method, c.group_id);
+      m += 2;
+    } else if (p[m] == "num_dos_points") {
+      if (m + 2 > p.size())
+        input_error("Not enough arguments for option 'num_dos_points'.");
+      if (!is_valid_int(p[m + 1], &c.num_dos_points))
+        input_error("number of DOS points should be an integer.");
+      if (c.num_dos_points < 1)
+        input_error("number of DOS points must be > 0.");
+      m += 1;
+      std::printf("    num_dos_points is %d.\n", c.num_dos_points);
+    } else {
+      input_error("Unrecognized argument in compute_dos.");
+    }
+  }
+  c.all_groups = c.grouping_method >= 0 && c.group_id < 0;
+  dos_ = c;
 }
 
 // RDF::parse (rdf.cu:264-333), with its messages
@@ -829,6 +890,11 @@ void Run::corr_open(ComputeCorr& c, int quantity, const char* name)
   // (the reference has this check for MSD only and divides by zero time origins in SDC::postprocess: refused here as well)
   if (c.num_corr > number_of_steps / c.interval)
     input_error(std::string(name) + " correlation times sampling interval should be <= number of MD steps.");
+  if (quantity == 2) { // DOS::initialize_parameters (dos.cu:284-288)
+    const double dt_in_ps = time_step * c.interval * TIME_UNIT_CONVERSION / 1000.0;
+    if (1.0 / dt_in_ps < c.omega_max / 3.14159265358979323846)
+      input_error("Velocity sampling rate < Nyquist frequency.");
+  }
   const int N = atom.number_of_atoms;
   std::vector<int> label;
   c.num_groups = 1;
@@ -850,8 +916,13 @@ void Run::corr_open(ComputeCorr& c, int quantity, const char* name)
   for (int k = 0; k < 9; ++k)
     c.cell[k] = box.cpu_h[k];
   nepmi_engine* e = force.engine();
-  die_on(nepmi_corr_create(e, quantity, N, c.interval, c.num_corr, label.empty() ? nullptr : label.data(), c.num_groups, &c.handle),
-         name);
+  if (quantity == 2) // the weights: DOS::copy_mass (dos.cu:326-336)
+    die_on(nepmi_corr_create_weighted(e, quantity, N, c.interval, c.num_corr, label.empty() ? nullptr : label.data(), c.num_groups,
+                                      atom.cpu_mass.data(), &c.handle),
+           name);
+  else
+    die_on(nepmi_corr_create(e, quantity, N, c.interval, c.num_corr, label.empty() ? nullptr : label.data(), c.num_groups, &c.handle),
+           name);
   die_on(nepmi_corr_attach(e, c.handle), name);
 }
 
@@ -872,6 +943,8 @@ void Run::corr_sample_stepwise()
     die_on(nepmi_corr_sample(msd_.handle, atom.unwrapped_position.data()), "corr_sample");
   if (sdc_.handle && corr_steps_ % sdc_.interval == 0)
     die_on(nepmi_corr_sample(sdc_.handle, atom.velocity_per_atom.data()), "corr_sample");
+  if (dos_.handle && corr_steps_ % dos_.interval == 0)
+    die_on(nepmi_corr_sample(dos_.handle, atom.velocity_per_atom.data()), "corr_sample");
   if (rdf_.handle && corr_steps_ % rdf_.interval == 0) {
     const int pbc[3] = {box.pbc_x, box.pbc_y, box.pbc_z};
     die_on(nepmi_rdf_sample(rdf_.handle, atom.position_per_atom.data(), box.cpu_h, pbc), "rdf_sample");
@@ -974,6 +1047,40 @@ void Run::write_sdc()
     std::fprintf(fid, "%g %g %g %g %g %g %g\n", l * dt_ps, vac[l] * vac_unit_conversion, vac[nc + l] * vac_unit_conversion,
                  vac[2 * nc + l] * vac_unit_conversion, sdc[l] * sdc_unit_conversion, sdc[nc + l] * sdc_unit_conversion,
                  sdc[2 * nc + l] * sdc_unit_conversion);
+  std::fclose(fid);
+}
+
+// DOS::postprocess (dos.cu:247-268): normalize_vac, output_vac, find_dos, output_dos
+void Run::write_dos()
+{
+  const ComputeCorr& c = dos_;
+  const int nc = c.num_corr, ng = c.num_groups, np = c.num_dos_points < 0 ? nc : c.num_dos_points;
+  std::vector<double> sums((size_t)ng * 3 * nc), mvac((size_t)ng * 3 * nc), dos((size_t)ng * 3 * np);
+  int64_t origins = 0, samples = 0;
+  die_on(nepmi_corr_read(c.handle, sums.data(), &origins, &samples), "corr_read");
+  const double dt_ps = time_step * c.interval * TIME_UNIT_CONVERSION / 1000.0;
+  std::vector<int64_t> size(c.atoms_per_group.begin(), c.atoms_per_group.end());
+  die_on(nepmi_dos_from_mvac(sums.data(), ng, nc, size.data(), dt_ps, c.omega_max, np, mvac.data(), dos.data()), "dos_from_mvac");
+  FILE* fid = std::fopen("mvac.out", "a");
+  if (!fid)
+    input_error("Cannot open mvac.out for writing.");
+  for (int g = 0; g < ng; ++g)
+    for (int l = 0; l < nc; ++l) {
+      const size_t o = (size_t)g * 3 * nc + l;
+      std::fprintf(fid, "%g %g %g %g\n", l * dt_ps, mvac[o], mvac[o + nc], mvac[o + 2 * nc]);
+    }
+  std::fflush(fid);
+  std::fclose(fid);
+  fid = std::fopen("dos.out", "a");
+  if (!fid)
+    input_error("Cannot open dos.out for writing.");
+  const double d_omega = c.omega_max / np;
+  for (int g = 0; g < ng; ++g)
+    for (int k = 0; k < np; ++k) {
+      const size_t o = (size_t)g * 3 * np + k;
+      std::fprintf(fid, "%g %g %g %g\n", d_omega + d_omega * k, dos[o], dos[o + np], dos[o + 2 * np]);
+    }
+  std::fflush(fid);
   std::fclose(fid);
 }
 
@@ -1466,6 +1573,7 @@ void Run::perform_a_run()
   corr_steps_ = 0;
   corr_open(msd_, 0, "MSD");
   corr_open(sdc_, 1, "SDC");
+  corr_open(dos_, 2, "DOS");
   rdf_open();
   adf_open();
   // target temperature of a temperature-dependent NEP (Run::parse_run, run.cu:679-681)
@@ -1559,10 +1667,13 @@ void Run::perform_a_run()
     write_msd("msd.out"); // MSD::postprocess
   if (sdc_.handle)
     write_sdc();
+  if (dos_.handle)
+    write_dos();
   if (rdf_.handle)
     write_rdf(); // RDF::postprocess
   corr_close(msd_);
   corr_close(sdc_);
+  corr_close(dos_);
   rdf_close();
   adf_close();
   const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -1708,6 +1819,8 @@ void Run::perform_a_run_dist()
     input_error("compute_msd is not available in multi-GPU runs (unwrapped positions are not tracked there).");
   if (sdc_.active)
     input_error("compute_sdc is not available in multi-GPU runs.");
+  if (dos_.active)
+    input_error("compute_dos is not available in multi-GPU runs.");
   if (rdf_.active)
     input_error("compute_rdf is not available in multi-GPU runs.");
   if (adf_.active)

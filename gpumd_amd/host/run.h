@@ -50,6 +50,11 @@ struct ComputeCorr {
   int num_atoms = 0, num_groups = 1;
   std::vector<int> atoms_per_group;
   double cell[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; // MSD::preprocess keeps the box of the run's start
+  // DOS (src/measure/dos.cuh): `compute_dos <interval> <Nc> <omega_max> [group <method> <id>] [num_dos_points <n>]`, a negative
+  // group id = every group of the method.  The mass-weighted sums are libnepmi's (quantity 2 of nepmi_corr_*, the weights from
+  // atom.cpu_mass), the normalisation and the transform nepmi_dos_from_mvac; mvac.out and dos.out are the host's.
+  double omega_max = 0.0;
+  int num_dos_points = -1;
 };
 
 // RDF (src/measure/rdf.cuh): `compute_rdf <rc> <num_bins> <interval>`.  The pair counts are libnepmi's (nepmi_rdf_*), sampled inside
@@ -117,6 +122,8 @@ private:
   void corr_sample_stepwise();
   void write_msd(const char* filename);
   void write_sdc();
+  void parse_compute_dos(const std::vector<std::string>& p);
+  void write_dos();
   void parse_compute_rdf(const std::vector<std::string>& p);
   void rdf_open();
   void rdf_close();
@@ -156,7 +163,7 @@ private:
   std::vector<DumpXyz> dump_xyzs;
   DumpObserver observer;
   ActiveLearning active_;
-  ComputeCorr msd_, sdc_;
+  ComputeCorr msd_, sdc_, dos_;
   ComputeRdf rdf_;
   ComputeAdf adf_;
   int corr_steps_ = 0; // finished steps of the run in progress (the paths that step by hand sample on it)

@@ -468,16 +468,33 @@ class NEP:
         self.set_option("generic", 1 if on else 0)
 
 
+def dos_from_mvac(lib, sums, group_size, dt_ps, omega_max, num_dos_points=None):
+    """nepmi_dos_from_mvac on host arrays: sums [G, 3, Nc], group_size [G] -> (omega [Np], mvac [G, 3, Nc], dos [G, 3, Np])"""
+    sums = np.ascontiguousarray(sums, dtype=np.float64)
+    ng, _, nc = sums.shape
+    npts = nc if num_dos_points is None else int(num_dos_points)
+    size = np.ascontiguousarray(group_size, dtype=np.int64)
+    if sums.shape[1] != 3 or size.shape != (ng,):
+        raise ValueError("sums: [G, 3, Nc], group_size: [G]")
+    mvac, dos = np.zeros((ng, 3, nc)), np.zeros((ng, 3, max(npts, 0)))
+    _capi.check(lib, lib.nepmi_dos_from_mvac(sums.ctypes.data_as(_capi.c_dp), ng, nc, size.ctypes.data_as(C.POINTER(_capi.c_i64)),
+                                             float(dt_ps), float(omega_max), npts, mvac.ctypes.data_as(_capi.c_dp),
+                                             dos.ctypes.data_as(_capi.c_dp)))
+    d_omega = float(omega_max) / npts
+    return d_omega + np.arange(npts) * d_omega, mvac, dos  # (as find_dos forms omega_k)
+
+
 class Correlator:
-    """Time-correlation sums (nepmi_corr_*): quantity "msd" (unwrapped positions) or "vac" (velocities), `num_corr` lags of
-    `interval` steps, optionally per group (`group_of_atom`: n ints in the caller's atom order, -1 = not sampled).
+    """Time-correlation sums (nepmi_corr_*): quantity "msd" (unwrapped positions), "vac" (velocities) or "mvac" (velocities, every
+    atom weighted by `weights`: n floats in the caller's atom order, the masses), `num_corr` lags of `interval` steps, optionally per
+    group (`group_of_atom`: n ints in the caller's atom order, -1 = not sampled).
 
     Attach it to the engine (`engine.attach(c)`) and the run_* methods sample it on the device; a host that steps by hand calls
     `sample(q)` with q = [3N] f64 on the device.  `read()` -> (sums [num_groups, 3, num_corr], num_origins, num_samples); the
-    reader normalises: MSD_l = sums / (atoms * origins)."""
-    QUANTITIES = {"msd": 0, "vac": 1}
+    reader normalises: MSD_l = sums / (atoms * origins).  An "mvac" correlator also has `dos(dt_ps, omega_max)`."""
+    QUANTITIES = {"msd": 0, "vac": 1, "mvac": 2}
 
-    def __init__(self, engine, quantity, interval, num_corr, group_of_atom=None, num_groups=1):
+    def __init__(self, engine, quantity, interval, num_corr, group_of_atom=None, num_groups=1, weights=None):
         self.engine = engine
         self.lib = engine.lib
         self.quantity = self.QUANTITIES[quantity] if isinstance(quantity, str) else int(quantity)
@@ -488,9 +505,20 @@ class Correlator:
             if g.shape != (engine.n,):
                 raise ValueError("group_of_atom: one int per atom")
             gp = g.ctypes.data_as(_capi.c_ip)
+            self.group_size = np.array([(g == k).sum() for k in range(self.num_groups)], dtype=np.int64)
+        else:
+            self.group_size = np.array([engine.n] + [0] * (self.num_groups - 1), dtype=np.int64)
         out = C.c_void_p()
-        _capi.check(self.lib, self.lib.nepmi_corr_create(engine.handle, self.quantity, engine.n, self.interval, self.num_corr, gp,
-                                                         self.num_groups, C.byref(out)))
+        if weights is None:  # (quantity 2 without weights: the library's refusal)
+            _capi.check(self.lib, self.lib.nepmi_corr_create(engine.handle, self.quantity, engine.n, self.interval, self.num_corr, gp,
+                                                             self.num_groups, C.byref(out)))
+        else:
+            w = np.ascontiguousarray(np.asarray(weights), dtype=np.float64)
+            if w.shape != (engine.n,):
+                raise ValueError("weights: one float per atom")
+            _capi.check(self.lib, self.lib.nepmi_corr_create_weighted(engine.handle, self.quantity, engine.n, self.interval,
+                                                                      self.num_corr, gp, self.num_groups,
+                                                                      w.ctypes.data_as(_capi.c_dp), C.byref(out)))
         self.handle = out
         if not hasattr(engine, "_correlators"):
             engine._correlators = weakref.WeakSet()
@@ -504,6 +532,14 @@ class Correlator:
         no, ns = C.c_int64(0), C.c_int64(0)
         _capi.check(self.lib, self.lib.nepmi_corr_read(self.handle, sums.ctypes.data_as(_capi.c_dp), C.byref(no), C.byref(ns)))
         return sums, int(no.value), int(ns.value)
+
+    def dos(self, dt_ps, omega_max, num_dos_points=None):
+        """"mvac" only: -> (omega [Np], mvac [num_groups, 3, num_corr] normalised to lag 0, dos [num_groups, 3, Np]) from the sums so
+        far (nepmi_dos_from_mvac); dt_ps = the time between two samples in ps, Np = num_dos_points or num_corr."""
+        if self.quantity != 2:
+            raise ValueError("dos: an \"mvac\" correlator only")
+        sums = self.read()[0]
+        return dos_from_mvac(self.lib, sums, self.group_size, dt_ps, omega_max, num_dos_points)
 
     def close(self):
         if getattr(self, "handle", None):

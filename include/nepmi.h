@@ -146,6 +146,27 @@ int nepmi_corr_sample(nepmi_corr* c, const double* q);
 int nepmi_corr_attach(nepmi_engine* e, nepmi_corr* c);
 int nepmi_corr_detach(nepmi_engine* e, nepmi_corr* c);
 int nepmi_corr_read(nepmi_corr* c, double* sums_host, int64_t* num_origins, int64_t* num_samples);
+/* ---- Phonon density of states (replaces DOS::process with gpu_find_vac, src/measure/dos.cu:84-143 and 220-245, and
+ *      normalize_vac / find_dos, dos.cu:414-427 and 450-481; the files belong to the reader).
+ *   quantity 2 (MVAC): per component sum_i (w_i * v_i(t)) * v_i(t - l), w_i a weight per atom: the mass.
+ * nepmi_corr_create_weighted makes a correlator of quantity 2, and of that quantity only (nepmi_corr_create refuses 2, and
+ * weights with quantity 0 or 1 are refused here).  weight_host: HOST array of n doubles in the caller's atom order, finite and
+ * not negative; the object keeps them on the device in its own atom order.  They are multiplied into the current frame once per
+ * sample, so a sample costs what a VAC sample costs.  Everything else -- groups, ring, counters, _sample, _attach, _read,
+ * lifetime, bit-reproducible sums -- is that of the block above; like a VAC correlator it samples the velocities and needs no
+ * unwrapped positions.
+ *   nepmi_dos_from_mvac: HOST only, no device work.  sums = what _read returned, [num_groups][3][num_corr]; group_size = atoms
+ * per group; dt_ps = the time between two samples in ps; omega_max in THz (angular).  Per group and component:
+ *   mvac_out[l] = sums[l] / sums[0]                                                    (what mvac.out holds),
+ *   dos_out[k]  = dt_ps * 2 * group_size * sum_l h_l mvac_out[l] cos(omega_k l dt_ps),  omega_k = (k + 1) omega_max / num_dos_points,
+ *   h_l = (cos(pi l / num_corr) + 1) / 2, doubled for l > 0 (the Hann window and the even extension to negative lags).
+ * A group and component whose sums[0] is zero (an empty group) gives zeros in both outputs; the reference prints 0 / 0. ---- */
+int nepmi_corr_create_weighted(
+  nepmi_engine* e, int quantity, int64_t n, int64_t sample_interval, int num_corr, const int* group_of_atom, int num_groups,
+  const double* weight_host, nepmi_corr** out);
+int nepmi_dos_from_mvac(
+  const double* sums, int num_groups, int num_corr, const int64_t* group_size, double dt_ps, double omega_max, int num_dos_points,
+  double* mvac_out, double* dos_out);
 /* ---- Radial distribution function sampled while the engine runs (replaces RDF::process / gpu_find_rdf_ON1,
  *      src/measure/rdf.cu:37-125, :178-202; the normalisation and the output, rdf.cu:204-251, belong to the reader).
  * Every unordered pair of atoms at its minimum-image distance d (apply_mic, src/model/box.cuh) counts if 0 < d^2 <= rc^2, in
