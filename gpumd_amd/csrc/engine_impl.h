@@ -1421,7 +1421,8 @@ private:
       b_.aidx = dalloc<unsigned short>((size_t)b_.MN_acomp * N);
       b_.amask = dalloc<unsigned>(4 * (size_t)N);
       // static window layout (Bufs::wtab comes with the cell arrays): list words of four LDS slots
-      b_.MN_wchunks = (b_.MN_ang + 3) / 4 + 2 * ((b_.MN_skin + 3) / 4) + 4;
+      // (two-type models: the two streams may hold list A's members too, option "angular_only_list_a" -- at worst all of one type)
+      b_.MN_wchunks = (b_.MN_ang + 3) / 4 + 2 * (((m.num_types == 2 ? b_.MN_ang : 0) + b_.MN_skin + 3) / 4) + 4;
       b_.wcode = dalloc<unsigned short>((size_t)b_.MN_wchunks * 4 * N);
       b_.wseg = dalloc<int>(N);
       b_.FPR = (m.n_max_radial + 1 + 3) / 4 * 4;
@@ -1787,7 +1788,8 @@ private:
     win2_ok_ = tile_ok_ && use_win2_ && b_.wtab != nullptr && win_.wmax < 65535;
     if (win2_ok_) {
       b_.wsent = win_.wmax;
-      be_.template launch<128>(kSlotMisc, N_, PackCodesBody{b_, shape_ts() == 2 ? 2 : 1});
+      aonly_built_ = aonly_list_a_active();
+      be_.template launch<128>(kSlotMisc, N_, PackCodesBody{b_, shape_ts() == 2 ? 2 : 1, (aonly_built_ && NEPMI_RW2_ABL != 4) ? 1 : 0});
       be_.d2h(flags, b_.flags, sizeof(flags));
       check_overflow(flags);
     }
@@ -2217,6 +2219,7 @@ public:
     ang_pair_trip_ = o.ang_pair_trip_;
     ang_flat_tables_ = o.ang_flat_tables_;
     lean_walks_ = o.lean_walks_;
+    aonly_list_a_ = o.aonly_list_a_;
     fold_seam_ = o.fold_seam_;
     brick_force_ = o.brick_force_;
     loop_ctx_ = o.loop_ctx_;
@@ -2336,6 +2339,19 @@ private:
       ensure_reverse_slots();
     B& rbe = radial_side_ ? *radial_side_ : be_; // (force_kernels_on: the boundary bricks on the communication stream)
     auto radial = [&](int64_t nb, int first) {
+      if constexpr (S::TS == 2) { // the streams hold list A's members too (PackCodesBody wrote them so at the rebuild)
+        if (win2 && aonly_built_ && !b_.use_rmask) {
+          if (b_.use_csync && lean_radial<S>())
+            rbe.launch_win2(kSlotRadial, nb, RadialWin2Body<S, 1, 1, 1>{ws2, md_, first, frozen});
+          else if (b_.use_csync)
+            rbe.launch_win2(kSlotRadial, nb, RadialWin2Body<S, 1, 0, 1>{ws2, md_, first, frozen});
+          else if (lean_radial<S>())
+            rbe.launch_win2(kSlotRadial, nb, RadialWin2Body<S, 0, 1, 1>{ws2, md_, first, frozen});
+          else
+            rbe.launch_win2(kSlotRadial, nb, RadialWin2Body<S, 0, 0, 1>{ws2, md_, first, frozen});
+          return;
+        }
+      }
       if (win2 && b_.use_csync && lean_radial<S>())
         rbe.launch_win2(kSlotRadial, nb, RadialWin2Body<S, 1, 1>{ws2, md_, first, frozen});
       else if (win2 && b_.use_csync)
@@ -2583,7 +2599,12 @@ public:
   }
   // 1: scatter-form steps of the run loops keep the per-step radial list as inside bits over the packed Verlet words
   // (Bufs::rmaskB) instead of compacting it; 0 (default): the compact list on every step.  Identical results, bit for bit.
-  void set_radial_mask(bool on) { use_rmask_ = on; }
+  void set_radial_mask(bool on)
+  {
+    if (on != use_rmask_ && aonly_list_a_)
+      have_list_ = false; // (the mask form reads the classic list words: "angular_only_list_a" resolves anew at the rebuild)
+    use_rmask_ = on;
+  }
   // 1 (default): scatter-form steps of the run loops keep the per-step radial list as wave-synchronous words (SyncFifo); 0: slot-major compact list
   void set_radial_sync(bool on) { use_csync_ = on; }
   // Guard band of the scatter form (nepmi_engine_set_scatter_guard): a pair half beyond `limit` eV/A (default 64; a net force
@@ -2669,6 +2690,20 @@ public:
   // and the scatter form walks the wave-synchronous words without weights or control flow for their padding places
   // (nep_scatter.h: LEAN); 0: the former bodies.  Same bits.
   void set_lean_list_walks(bool on) { lean_walks_ = on; }
+  // 1 (default): two-type shapes on the static window layout keep the members of list A in the two type-pure streams as well,
+  // and the radial pass walks list A for the angular membership alone (nep_window.h: RadialWin2Body<S, SYNC, LEAN, 1>); 0: list A
+  // carries its own radial work.  Same radial sums, forces and energies bit for bit; the entries of the per-step compact list
+  // leave in another order (the scatter form's float virial may move in its last bits).  The layout is one per engine and is
+  // written at the list rebuild, so a change asks for one.
+  void set_angular_only_list_a(bool on)
+  {
+    if (on != aonly_list_a_)
+      have_list_ = false;
+    aonly_list_a_ = on;
+  }
+  // ... where it applies: two register-resident types, and no reader of the classic list words (the mask form of the per-step
+  // radial list, option "radial_mask", walks list B's rows by their position)
+  bool aonly_list_a_active() const { return aonly_list_a_ && shape_ts() == 2 && !use_rmask_; }
   // ... the radial pass: shapes with packed per-type sums (one type: the clamp only; many types are not packed)
   template <class S>
   bool lean_radial() const
@@ -2829,6 +2864,7 @@ public:
       s += recompute_s() ? " angular_sums=recomputed" : " angular_sums=stored";
     }
     s += (tile_ok_ && win2 && shape_ts() > 0 && lean_walks_) ? " list_walks=lean" : " list_walks=classic";
+    s += (tile_ok_ && win2 && aonly_built_) ? " list_a=angular_only" : " list_a=classic";
     s += (last_scatter_form_ && last_mask_form_)   ? " radial_list=inside_bits_over_the_verlet_words"
          : (last_scatter_form_ && last_sync_form_) ? " radial_list=wave_synchronous_words"
                                                    : " radial_list=compacted";
@@ -2909,6 +2945,9 @@ private:
   bool ang_flat_tables_ = !(std::getenv("NEPMI_ANGULAR_FLAT_TABLES") && std::atoi(std::getenv("NEPMI_ANGULAR_FLAT_TABLES")) == 0);
   // set_lean_list_walks; NEPMI_LEAN_LIST_WALKS=0 in the environment: the default of engines no caller can reach
   bool lean_walks_ = !(std::getenv("NEPMI_LEAN_LIST_WALKS") && std::atoi(std::getenv("NEPMI_LEAN_LIST_WALKS")) == 0);
+  // set_angular_only_list_a; NEPMI_ANGULAR_ONLY_LIST_A=0 in the environment: the default of engines no caller can reach
+  bool aonly_list_a_ = !(std::getenv("NEPMI_ANGULAR_ONLY_LIST_A") && std::atoi(std::getenv("NEPMI_ANGULAR_ONLY_LIST_A")) == 0);
+  bool aonly_built_ = false; // the list words of the last rebuild hold list A's members in the streams
   float* fused_img_flat_ = nullptr; // the flat-table image (the first form stays in fused_img_: the per-brick kernel reads it)
   size_t fused_img_flat_floats_ = 0;
   bool fused_img_flat_stale_ = true;

@@ -185,7 +185,8 @@ struct Bufs {
   //   wcode[(chunk * N + k) * 4 + u]: list A (its own order), then list B -- for two-type shapes first the neighbours of
   //   type 0 and of type 1 as word pairs (row 2p: four of type 0, row 2p + 1: four of type 1) -- every segment padded to
   //   whole words with the sentinel slot `wsent` (a record far outside every cutoff); wseg[k] = words of A | words (word
-  //   pairs) of B << 8
+  //   pairs) of B << 8.  Two-type shapes with engine option "angular_only_list_a": the two streams hold list A's members too,
+  //   each at the front of the stream of its type in list order (PackCodesBody: aonly); list A's own words are unchanged
   int* wtab;
   unsigned short* wcode;
   int* wseg;
@@ -1001,10 +1002,13 @@ struct BrickOrderBody {
 };
 
 // Verlet entries as static LDS slots, packed four to a word (Bufs::wcode): one work-item per atom, at the rebuild, after
-// TileStatsBody has tabulated the windows.  parts = 2: list B split by the neighbour's type (two-type shapes).
+// TileStatsBody has tabulated the windows.  parts = 2: list B split by the neighbour's type (two-type shapes).  aonly (parts = 2;
+// engine option "angular_only_list_a"): the two streams hold the members of list A too -- each at the front of the stream of
+// its type, in list order, list B's members behind them -- and list A's own words stay as they are (RadialWin2Body<.., AONLY>).
 struct PackCodesBody {
   Bufs b;
   int parts;
+  int aonly;
   NEPMI_HD void operator()(int64_t k) const
   {
     const int64_t N = b.N;
@@ -1084,13 +1088,21 @@ struct PackCodesBody {
     if (parts == 2) {
       // two type-pure streams, word by word side by side: row wa + 2p = four neighbours of type 0, row wa + 2p + 1 = four of
       // type 1; the shorter stream is padded with sentinel words
-      int s0 = 0, s1 = 0; // cursors over list B: next entry of type 0 / of type 1
+      // the streams' source: list B, with aonly list A in front of it (entry s < n0: list A's entry s, else list B's s - n0)
+      const int n0 = aonly ? na : 0, nv = n0 + nb;
+      auto type_of = [&](int s) -> bool {
+        return b.posq[s < n0 ? b.nl_ang[(int64_t)s * N + k] : b.nl_skin[(int64_t)(s - n0) * N + k]].type != 0;
+      };
+      auto code_of = [&](int s) -> unsigned {
+        return s < n0 ? b.code_ang[(int64_t)s * N + k] : b.code_skin[(int64_t)(s - n0) * N + k];
+      };
+      int s0 = 0, s1 = 0; // cursors over the source: next entry of type 0 / of type 1
       // the types of the entries, looked up once (bit s: entry s is not of type 0); lists longer than the mask use the look-up
       unsigned long long m0 = 0ull, m1 = 0ull, m2 = 0ull, m3 = 0ull; // (four scalars: no dynamically indexed register array)
-      const bool masked = nb <= 256;
+      const bool masked = nv <= 256;
       if (masked)
-        for (int s = 0; s < nb; ++s) {
-          const unsigned long long bit = (b.posq[b.nl_skin[(int64_t)s * N + k]].type != 0 ? 1ull : 0ull) << (s & 63);
+        for (int s = 0; s < nv; ++s) {
+          const unsigned long long bit = (type_of(s) ? 1ull : 0ull) << (s & 63);
           const int w = s >> 6;
           m0 |= w == 0 ? bit : 0ull;
           m1 |= w == 1 ? bit : 0ull;
@@ -1104,13 +1116,13 @@ struct PackCodesBody {
       };
       auto next_of = [&](int& s, int want) -> int {
         if (masked) {
-          while (s < nb && other(s) != (want != 0))
+          while (s < nv && other(s) != (want != 0))
             ++s;
         } else {
-          while (s < nb && (b.posq[b.nl_skin[(int64_t)s * N + k]].type != 0) != (want != 0))
+          while (s < nv && type_of(s) != (want != 0))
             ++s;
         }
-        return s < nb ? s++ : -1;
+        return s < nv ? s++ : -1;
       };
       for (;;) {
         int e0[4], e1[4];
@@ -1121,9 +1133,9 @@ struct PackCodesBody {
         if (e0[0] < 0 && e1[0] < 0)
           break;
         for (int u = 0; u < 4; ++u)
-          put(e0[u] >= 0 ? slot_of(b.code_skin[(int64_t)e0[u] * N + k]) : (unsigned short)b.wsent);
+          put(e0[u] >= 0 ? slot_of(code_of(e0[u])) : (unsigned short)b.wsent);
         for (int u = 0; u < 4; ++u)
-          put(e1[u] >= 0 ? slot_of(b.code_skin[(int64_t)e1[u] * N + k]) : (unsigned short)b.wsent);
+          put(e1[u] >= 0 ? slot_of(code_of(e1[u])) : (unsigned short)b.wsent);
         ++wb;
       }
     } else {

@@ -816,7 +816,8 @@ struct RadialWinBody {
 #define NEPMI_BUILD_WIN 1 // the Verlet lists of a rebuild from LDS windows (BuildListsWinBody) where the window kernels apply; 0: BuildListsBody
 #endif
 #ifndef NEPMI_RW2_ABL
-#define NEPMI_RW2_ABL 0 // ablation builds (timings only): 1 = no compact-list stores, 2 = no stores and no counters, 3 = no angular record stores
+#define NEPMI_RW2_ABL 0 // ablation builds (timings only): 1 = no compact-list stores, 2 = no stores and no counters, 3 = no angular record stores,
+                        // 4 = the AONLY body on the classic list words (list A's radial work is not done anywhere: what it costs)
 #endif
 #ifndef NEPMI_RW2_HALF
 #define NEPMI_RW2_HALF 1 // 1: a word pair is processed as two halves of 2 + 2 candidates (fewer live registers), 0: 4 + 4 at once
@@ -901,8 +902,14 @@ constexpr int kListModeLean = 4; // launch_force_scatter: or-ed to list mode 2 =
 // once each, and adds each to the half of its type with a broadcast of its own half of the packed basis (the same two fma per
 // half of SS on the same operands in the same order as LEAN = 0, which evaluates every candidate in both halves); the
 // clamp of the distance is one v_min_u32 (nep_dev.h: clamp_to_cutoff).
-template <class S, int SYNC = 0, int LEAN = 0>
+// AONLY (engine option "angular_only_list_a"; two-type shapes on the layout PackCodesBody writes with aonly = 1): the members of
+// list A stand in the two type-pure streams as well, in front of list B's, so the walk over list A decides the angular
+// membership alone -- one cutoff, its own near-band test -- and the stream loop does all the radial work at its own rate (one
+// packed basis per two candidates, no weights, no branch on the neighbour's type).  Each half of SS takes the same members in
+// the same order as before: the radial sums keep their bits.
+template <class S, int SYNC = 0, int LEAN = 0, int AONLY = 0>
 struct RadialWin2Body {
+  static_assert(AONLY == 0 || S::TS == 2, "AONLY: two-type shapes only");
   WinStage st;
   ModelD m;
   int first;         // workgroup w runs brick_order[first + w] (first < 0: brick w)
@@ -1010,6 +1017,31 @@ struct RadialWin2Body {
         const float d2e = pair_geometry(st.box, p1, b.posq[(unsigned)c.rw & (unsigned)kIdxMask], ex, ey, ez);
         c.inside = d2e < rc * rc;
         c.ang = list_a && d2e < rca * rca;
+      }
+    };
+    // AONLY: list A against the angular cutoff alone (the streams judge the same slot against the radial one)
+    auto judge_ang = [&](int slot, bool& nearband) __attribute__((always_inline)) -> Cand {
+      Cand c;
+      const WinRec r = wrec[slot];
+      c.slot = slot;
+      c.rw = r.w;
+      c.fx = (float)(r.x - ox);
+      c.fy = (float)(r.y - oy);
+      c.fz = (float)(r.z - oz);
+      c.d2 = dot3f(c.fx, c.fx, c.fy, c.fy, c.fz, c.fz) * unit2;
+      const float rca = m.uniform_rc ? m.rc_a_max : (rca1 + m.rc_a[(unsigned)r.w >> kIdxBits]) * 0.5f;
+      const float ea = c.d2 - rca * rca;
+      c.inside = false;
+      c.ang = ea < 0.0f;
+      nearband = nearband || fabsf(ea) < band;
+      return c;
+    };
+    auto retake_ang = [&](Cand& c) __attribute__((always_inline)) {
+      const float rca = m.uniform_rc ? m.rc_a_max : (rca1 + m.rc_a[(unsigned)c.rw >> kIdxBits]) * 0.5f;
+      if (fabsf(c.d2 - rca * rca) < band && c.slot != b.wsent) {
+        float ex, ey, ez;
+        const float d2e = pair_geometry(st.box, p1, b.posq[(unsigned)c.rw & (unsigned)kIdxMask], ex, ey, ez);
+        c.ang = d2e < rca * rca;
       }
     };
     // The compact radial list.  NEPMI_CW: words of four slots, staged in two registers per stream and stored as 8 bytes when
@@ -1296,7 +1328,8 @@ struct RadialWin2Body {
       return v;
     };
 
-    // ---- list A: angular membership + radial sums; words 0 .. wa-1 (two candidates at a time: register budget) ----
+    // ---- list A: angular membership + radial sums (AONLY: the membership alone); words 0 .. wa-1 (two candidates at a time:
+    //      register budget) ----
     {
       U2w w1 = load_word(0, wa), w2 = load_word(1, wa);
       for (int w = 0; w < wa; ++w) {
@@ -1308,11 +1341,20 @@ struct RadialWin2Body {
           const unsigned pr = hh == 0 ? cur.lo : cur.hi;
           bool nearband = false;
           Cand c[2];
-          c[0] = judge((int)(pr & 0xFFFFu), true, nearband);
-          c[1] = judge((int)(pr >> 16), true, nearband);
-          if (nearband) {
-            retake(c[0], true);
-            retake(c[1], true);
+          if (AONLY) {
+            c[0] = judge_ang((int)(pr & 0xFFFFu), nearband);
+            c[1] = judge_ang((int)(pr >> 16), nearband);
+            if (nearband) {
+              retake_ang(c[0]);
+              retake_ang(c[1]);
+            }
+          } else {
+            c[0] = judge((int)(pr & 0xFFFFu), true, nearband);
+            c[1] = judge((int)(pr >> 16), true, nearband);
+            if (nearband) {
+              retake(c[0], true);
+              retake(c[1], true);
+            }
           }
           if (ASYNC) { // (a half brings at most two: no lane enters it with more than six waiting)
             while (NEPMI_WAVE_ANY(qa.p > 6))
@@ -1353,12 +1395,16 @@ struct RadialWin2Body {
             }
             if (!ASYNC && !b.use_amask && live)
               amap[(int64_t)idx * N] = cs;
+            if (AONLY)
+              continue; // (the radial queues fill in the stream loop)
             if (S::TS == 2 && ((unsigned)c[u].rw >> kIdxBits) == 1u)
               push_back(c[u], 4 * (w & 7) + 2 * hh + u);
             else
               push_front(c[u], 4 * (w & 7) + 2 * hh + u);
           }
-          if (S::TS > 0 && !ZIP) { // one type: the two candidates side by side
+          if (AONLY) {
+            // no radial sums here
+          } else if (S::TS > 0 && !ZIP) { // one type: the two candidates side by side
             f2 fn[S::KRM + 1];
             basis2(c[0], c[1], fn);
 #pragma unroll
@@ -1396,6 +1442,8 @@ struct RadialWin2Body {
             accumulate1(c[1]);
           }
         }
+        if (AONLY)
+          continue; // (no radial entry was queued: nothing to store, no mask word -- the mask form keeps the classic layout)
         if (!SYNC && b.use_rmask && ((w & 7) == 7 || w == wa - 1)) {
           if ((w >> 3) < b.MAW)
             b.rmaskA[(int64_t)(w >> 3) * N + k] = mcur;

@@ -168,6 +168,6 @@ class DistMD:
 
     def engine_describe(self):
         """the kernel forms the local engine's last force evaluation ran (nepmi_engine_describe)"""
-        buf = C.create_string_buffer(512)
-        n = self.lib.nepmi_engine_describe(self.lib.nepmi_dist_engine(self.handle), buf, 512)
+        buf = C.create_string_buffer(1024)
+        n = self.lib.nepmi_engine_describe(self.lib.nepmi_dist_engine(self.handle), buf, 1024)
         return buf.value.decode() if n >= 0 else ""

@@ -428,6 +428,14 @@ class NEP:
         the scatter form) or by the former bodies (option "lean_list_walks"); bit-identical results"""
         self.set_option("lean_list_walks", 1 if on else 0)
 
+    def set_angular_only_list_a(self, on=True):
+        """two-type shapes: the members of list A stand in the two type-pure streams of the static window layout as well and
+        the radial pass walks list A for the angular membership alone (default), or list A carries its own radial work
+        (option "angular_only_list_a"); radial sums, energies and forces bit-identical, the scatter form's float virial to
+        its last bits (the per-step compact list leaves in another order).  Takes effect at the next list rebuild, which it
+        asks for."""
+        self.set_option("angular_only_list_a", 1 if on else 0)
+
     def set_fold_seam(self, on=True):
         """single-domain NVE run loops in the scatter form: the fold of the window sums inside the integrator pass behind it
         (default), or as a launch of its own (option "fold_seam"); bit-identical results (a window sum too large for the seam
@@ -437,8 +445,8 @@ class NEP:
     def describe(self):
         """the kernel forms the last force evaluation ran (counted rules of the engine, as text)"""
         import ctypes as C
-        buf = C.create_string_buffer(512)
-        n = self.lib.nepmi_engine_describe(self.handle, buf, 512)
+        buf = C.create_string_buffer(1024)
+        n = self.lib.nepmi_engine_describe(self.handle, buf, 1024)
         if n < 0:
             self._ck(n)
         return buf.value.decode()

@@ -672,6 +672,22 @@ int nepmi_engine_set_virial_mode(nepmi_engine* e, int mode);
  *       not relied on (it is not exactly zero for every cutoff).  Only products with 1 and sums with 0 are left out: results equal
  *       under numpy.array_equal for every cutoff (tests/test_lean_list_walks.py).
  *       Many-type shapes are not touched.  NEPMI_LEAN_LIST_WALKS=0 in the environment sets the default of engines no caller reaches.
+ *   "angular_only_list_a": two-type compiled shapes on the static window layout: value = 1 (default) -- the list rebuild writes the
+ *       members of list A (the candidates within the angular cutoff + skin) into the two type-pure streams of the packed list
+ *       words as well, each at the front of the stream of its type, in list order, list B's members behind them, and the radial
+ *       pass walks list A for the angular membership alone (one cutoff, its own near-band test, the angular records); all radial
+ *       work -- basis, sums, the per-step compact list -- is done in the stream loop, which serves one neighbour of each type with
+ *       one packed evaluation and knows no per-type weights or branches.  0: list A carries its own radial work, mixed types in
+ *       list order.  Each half of the packed radial sums takes the same members in the same order either way: descriptors,
+ *       energies, forces (fixed-point sums) and with them the positions and velocities of NVE / NVT runs are equal under
+ *       numpy.array_equal.  The entries of an atom's wave-synchronous words leave in another order (and in fewer padded rows),
+ *       and the scatter form sums its per-atom float virial in walk order: virials and the pressure of the thermo rows may move
+ *       in their last bits, and a barostat run (npt_ber, npt_scr), whose box follows the pressure, with them
+ *       (tests/test_angular_only_list_a.py bounds the move by the distance between the scatter and the gather form).
+ *       The layout is one per engine, written at the list rebuild: setting the option asks for one.  It resolves to 0 -- and
+ *       nepmi_engine_describe says list_a=classic -- for one-type, many-type and run-time shapes and while "radial_mask" is set
+ *       (the mask form walks list B's rows by their position).  NEPMI_ANGULAR_ONLY_LIST_A=0 in the environment sets the default
+ *       of engines no caller reaches.
  *   "fold_seam": Single-domain NVE run loops whose force assembly takes the scatter form: value = 1 (default) -- the fold of the
  *       window sums (one atom's entries of the up to eight brick windows that hold it) runs inside the integrator pass behind it
  *       (second half-kick of the step, and on a step that neither records thermo data nor ends the call the first half-kick, drift,
