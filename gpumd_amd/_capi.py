@@ -142,6 +142,14 @@ SYMBOLS = {
     "nepmi_adf_set_lds_budget": (C.c_int, [VP, c_i64]),
     "nepmi_adf_form": (C.c_int, [VP]),
     "nepmi_adf_capacity": (C.c_int, []),
+    "nepmi_orient_create": (C.c_int, [VP, c_i64, C.c_int, C.c_double, C.c_int, c_ip, C.c_int, C.c_int, C.c_int, C.c_int, c_i64,
+                                      C.POINTER(VP)]),
+    "nepmi_orient_destroy": (None, [VP]),
+    "nepmi_orient_sample": (C.c_int, [VP, VP, c_dp, c_ip]),
+    "nepmi_orient_attach": (C.c_int, [VP, VP]),
+    "nepmi_orient_detach": (C.c_int, [VP, VP]),
+    "nepmi_orient_read": (C.c_int, [VP, c_dp, c_dp, c_ip, C.POINTER(c_i64)]),
+    "nepmi_orient_capacity": (C.c_int, []),
     "nepmi_transport_rccl_id": (C.c_int, [C.c_char_p]),
     "nepmi_transport_rccl": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(NepmiTransport)]),
     "nepmi_transport_tcp": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(NepmiTransport)]),

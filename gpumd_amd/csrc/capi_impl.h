@@ -45,6 +45,11 @@ struct nepmi_adf {
   nepmi::AdfT<NepmiBackend>* a;
 };
 
+struct nepmi_orient {
+  const nepmi_api* api;
+  nepmi::OrientT<NepmiBackend>* o;
+};
+
 namespace {
 
 thread_local std::string g_last_error;
@@ -939,6 +944,75 @@ int nepmi_adf_form(nepmi_adf* a)
 }
 
 int nepmi_adf_capacity(void) { return nepmi::kAdfMaxNeighbours; }
+
+int nepmi_orient_create(
+  nepmi_engine* e, int64_t n, int mode, double rc, int nnn, const int* degrees, int num_degrees, int average, int wl, int wlhat,
+  int64_t sample_interval, nepmi_orient** out)
+{
+  if (!e || !out)
+    return fail(NEPMI_ERR_ARG, "null argument");
+  *out = nullptr;
+  nepmi_orient* o = new nepmi_orient();
+  o->api = NEPMI_SELF_API;
+  o->o = nullptr;
+  const int st = guarded([&] {
+    if (n != e->e->num_atoms())
+      throw nepmi::EngineError{NEPMI_ERR_ARG, "orient: n is not the engine's number of atoms"};
+    o->o = new nepmi::OrientT<NepmiBackend>(e->e->backend(), n, mode, rc, nnn, degrees, num_degrees, average, wl, wlhat, sample_interval);
+  });
+  if (st != NEPMI_OK) {
+    delete o;
+    return st;
+  }
+  *out = o;
+  return NEPMI_OK;
+}
+
+void nepmi_orient_destroy(nepmi_orient* o)
+{
+  if (!o)
+    return;
+  if (o->o && o->o->attached_to)
+    guarded([&] { static_cast<nepmi::EngineT<NepmiBackend>*>(o->o->attached_to)->orient_detach(o->o); });
+  guarded([&] { delete o->o; });
+  delete o;
+}
+
+int nepmi_orient_sample(nepmi_orient* o, const double* pos, const double* h9, const int* pbc3)
+{
+  if (!o || !pos || !h9 || !pbc3)
+    return fail(NEPMI_ERR_ARG, "null argument");
+  return guarded([&] {
+    nepmi::BoxD box;
+    nepmi::box_from_h9(h9, pbc3, box);
+    o->o->sample_now(pos, box);
+  });
+}
+
+int nepmi_orient_attach(nepmi_engine* e, nepmi_orient* o)
+{
+  if (!e || !o)
+    return fail(NEPMI_ERR_ARG, "null argument");
+  if (o->api != e->api)
+    return fail(NEPMI_ERR_ARG, "orient: created from an engine of another kernel library");
+  return guarded([&] { e->e->orient_attach(o->o); });
+}
+
+int nepmi_orient_detach(nepmi_engine* e, nepmi_orient* o)
+{
+  if (!e || !o)
+    return fail(NEPMI_ERR_ARG, "null argument");
+  return guarded([&] { e->e->orient_detach(o->o); });
+}
+
+int nepmi_orient_read(nepmi_orient* o, double* last_host, double* sum_host, int* nn_host, int64_t* num_samples)
+{
+  if (!o)
+    return fail(NEPMI_ERR_ARG, "null orient handle");
+  return guarded([&] { o->o->read(last_host, sum_host, nn_host, num_samples); });
+}
+
+int nepmi_orient_capacity(void) { return nepmi::kOrientMaxNeighbours; }
 
 int nepmi_engine_set_option(nepmi_engine* e, const char* name, double value)
 {

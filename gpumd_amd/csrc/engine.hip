@@ -1290,6 +1290,20 @@ struct HipBackend {
       launch_adf_triplets_form<false>(a, n, words, lds_bytes);
   }
 
+  // q_lm of one orientational-order sample (nep_orient.h): the first pass, or the neighbour average over its rows
+  static constexpr bool kHasOrient = true;
+  void launch_orient_qlm(const OrientArgs& a, int64_t n, bool average)
+  {
+    if (n <= 0)
+      return;
+    const unsigned grid = (unsigned)std::min<int64_t>((n + kOrientWaves - 1) / kOrientWaves, 2 * 256); // two workgroups share a CU's LDS
+    if (average)
+      hipLaunchKernelGGL((nepmi_orient_qlm<true>), dim3(grid), dim3(kOrientLanes), 0, stream, a, n, frozen);
+    else
+      hipLaunchKernelGGL((nepmi_orient_qlm<false>), dim3(grid), dim3(kOrientLanes), 0, stream, a, n, frozen);
+    NEPMI_HIP_CHECK(hipGetLastError());
+  }
+
   // ANN launch: the MFMA kernel when the shape fits (few types, <= 128 neurons, <= 128 output rows
   // incl. the radial-table rows), else the per-atom AnnBody.
   template <int MT, int QB, bool BYTYPE = false>

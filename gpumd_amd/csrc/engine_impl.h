@@ -10,6 +10,7 @@
 #include "nep_corr.h"
 #include "nep_rdf.h"
 #include "nep_adf.h"
+#include "nep_orient.h"
 #include "nep_model.h"
 #include "nep_window.h"
 #include "nep_highl.h"
@@ -726,6 +727,7 @@ public:
     corr_check(n);
     rdf_check(n);
     adf_check(n);
+    orient_check(n);
     if ((is_small_box(box) && model_.kind == 0) || (stepwise_loops_ && (ens == kLan || ens == kBao))) {
       // (set_stepwise_loops: the Langevin ensembles as the plain sequence of the per-call entry points on the caller's
       // arrays -- what the resident forms are checked against, bit for bit)
@@ -1012,11 +1014,14 @@ public:
         rdf_sample_step(step, nullptr, b_.posq, b_.perm, N_, box_, frozen);
       if (!adfs_.empty()) // (last of the step's launches; positions only, the step's box)
         adf_sample_step(step, nullptr, b_.posq, b_.perm, N_, box_, frozen);
+      if (!orients_.empty()) // (after the ADF handles: the last of the step's launches)
+        orient_sample_step(step, nullptr, b_.posq, b_.perm, N_, box_, frozen);
       ++step;
     }
     corr_advance(nsteps);
     rdf_advance(nsteps);
     adf_advance(nsteps);
+    orient_advance(nsteps);
     num_compute = compute0 + nsteps;
     calm_steps_ = nsteps - calm_since;
     if (virial)
@@ -1123,11 +1128,14 @@ public:
         rdf_sample_step(step, pos, nullptr, nullptr, n, box, nullptr);
       if (!adfs_.empty())
         adf_sample_step(step, pos, nullptr, nullptr, n, box, nullptr);
+      if (!orients_.empty())
+        orient_sample_step(step, pos, nullptr, nullptr, n, box, nullptr);
     }
     if (nsteps > 0) {
       corr_advance(nsteps);
       rdf_advance(nsteps);
       adf_advance(nsteps);
+      orient_advance(nsteps);
     }
     be_.sync();
     int flags[kNumFlags];
@@ -1271,6 +1279,24 @@ private:
       r->advance(nsteps);
   }
   std::vector<AdfT<B>*> adfs_;
+  void orient_check(int64_t n) const
+  {
+    for (const OrientT<B>* r : orients_)
+      if (r->n() != n)
+        throw EngineError{-4, "an attached orientational-order handle was created for another number of atoms"};
+  }
+  void orient_sample_step(int64_t step, const double* pos, const PosQ* posq, const int* perm, int64_t n, const BoxD& box, const int* frozen)
+  {
+    for (OrientT<B>* r : orients_)
+      if (r->sample_after(step))
+        r->sample(pos, posq, perm, n, box, frozen);
+  }
+  void orient_advance(int64_t nsteps)
+  {
+    for (OrientT<B>* r : orients_)
+      r->advance(nsteps);
+  }
+  std::vector<OrientT<B>*> orients_;
 
   template <class T>
   T* dalloc(size_t count)
@@ -2165,6 +2191,29 @@ public:
         return;
       }
     throw EngineError{-4, "adf: not attached to this engine"};
+  }
+  // orientational-order handles (nep_orient.h): the rules of the ADF handles above; they sample after them
+  void orient_attach(OrientT<B>* r)
+  {
+    if (r->n() > cap_)
+      throw EngineError{-4, "orient: more atoms than the engine's capacity"};
+    for (OrientT<B>* o : orients_)
+      if (o == r)
+        throw EngineError{-4, "orient: already attached"};
+    if (r->attached_to)
+      throw EngineError{-4, "orient: attached to another engine"};
+    orients_.push_back(r);
+    r->attached_to = this;
+  }
+  void orient_detach(OrientT<B>* r)
+  {
+    for (size_t i = 0; i < orients_.size(); ++i)
+      if (orients_[i] == r) {
+        orients_.erase(orients_.begin() + i);
+        r->attached_to = nullptr;
+        return;
+      }
+    throw EngineError{-4, "orient: not attached to this engine"};
   }
   void check_flags_now()
   {

@@ -440,6 +440,8 @@ void Run::parse_one_keyword(const std::vector<std::string>& p)
     parse_compute_rdf(p);
   } else if (k == "compute_adf") {
     parse_compute_adf(p);
+  } else if (k == "compute_orientorder") {
+    parse_compute_orientorder(p);
   } else if (k == "run") {
     if (p.size() != 2)
       input_error("run should have 1 parameter.");
@@ -461,6 +463,7 @@ void Run::parse_one_keyword(const std::vector<std::string>& p)
     dos_ = ComputeCorr();
     rdf_ = ComputeRdf();
     adf_ = ComputeAdf();
+    orient_ = ComputeOrient();
   } else {
     input_error("'" + k + "' is invalid keyword (or outside the path gpumd-mi covers).");
   }
@@ -882,6 +885,142 @@ void Run::write_adf(int step)
   std::fclose(fid);
 }
 
+// OrientOrder::parse (orientorder.cu:798-917), with its acceptance and its messages: with no token after the degrees it stops
+// with "Number of paramaters exceeds ..."; one token after wlhat is accepted and ignored
+void Run::parse_compute_orientorder(const std::vector<std::string>& p)
+{
+  std::printf("Compute Steinhardt bond-orientational order parameters.\n");
+  if (orient_.active)
+    input_error("compute_orientorder can be used once in a run.");
+  ComputeOrient c;
+  c.active = true;
+  const int num_param = (int)p.size();
+  if (num_param < 6)
+    input_error("compute_orientorder should have at least 5 parameters.");
+  if (!is_valid_int(p[1], &c.interval))
+    input_error("interval step per sample should be an integer.");
+  if (c.interval <= 0)
+    input_error("interval step per sample should be positive.");
+  if (p[2] == "cutoff") {
+    c.mode = 0;
+    if (!is_valid_real(p[3], &c.rc) || c.rc <= 0.)
+      input_error("cutoff should be an positive float.");
+  } else if (p[2] == "nnn") {
+    c.mode = 1;
+    c.rc = 6.0; // the reference's search radius of this mode (orientorder.cuh:71)
+    if (!is_valid_int(p[3], &c.nnn) || c.nnn <= 0)
+      input_error("nnn should be an positive integer.");
+  } else {
+    input_error("mode_type should be cutoff or nnn.");
+  }
+  int ndegrees = 0;
+  if (!is_valid_int(p[4], &ndegrees) || ndegrees <= 0)
+    input_error("ndegrees should be an positive integer.");
+  if (num_param < 5 + (int64_t)ndegrees)
+    input_error("Must include " + std::to_string(ndegrees) + " degrees.");
+  for (int i = 1; i < ndegrees + 1; ++i) {
+    int degree = 0;
+    if (!is_valid_int(p[4 + i], &degree) || degree < 0)
+      input_error("Degree " + std::to_string(i) + " should be an positive integer.");
+    c.degrees.push_back(degree);
+  }
+  if (num_param > 5 + ndegrees && num_param < 5 + ndegrees + 5) {
+    int v = 0;
+    if (!is_valid_int(p[4 + ndegrees + 1], &v))
+      input_error("average should be 1 or 0.");
+    c.average = v != 0;
+    if (num_param > 5 + ndegrees + 1) {
+      if (!is_valid_int(p[4 + ndegrees + 2], &v))
+        input_error("wl should be 1 or 0.");
+      c.wl = v != 0;
+    }
+    if (num_param > 5 + ndegrees + 2) {
+      if (!is_valid_int(p[4 + ndegrees + 3], &v))
+        input_error("wlhat should be 1 or 0.");
+      c.wlhat = v != 0;
+    }
+  } else {
+    input_error("Number of paramaters exceeds " + std::to_string(5 + ndegrees + 4) + ".");
+  }
+  // (ours: the reference takes any number of degrees of any size until its factorial table ends)
+  if (ndegrees > 8)
+    input_error("compute_orientorder takes at most 8 degrees.");
+  for (int l : c.degrees)
+    if (l > 12)
+      input_error("compute_orientorder takes degrees up to 12.");
+  std::printf("    every %d steps, \n", c.interval);
+  if (c.mode == 0)
+    std::printf("    with %f angstrom cutoff,\n", c.rc);
+  else
+    std::printf("    with %d nearest neighbor atoms,\n", c.nnn);
+  std::printf(ndegrees > 1 ? "    with %d degrees:" : "    with %d degree:", ndegrees);
+  for (int l : c.degrees)
+    std::printf(" %d", l);
+  std::printf(",\n");
+  std::printf("    average is %s, wl is %s and wlhat is %s.\n", c.average ? "true" : "false", c.wl ? "true" : "false",
+              c.wlhat ? "true" : "false");
+  orient_ = c;
+}
+
+// OrientOrder::preprocess (orientorder.cu:575-635): the handle of this run, attached to the engine
+void Run::orient_open()
+{
+  if (!orient_.active)
+    return;
+  nepmi_engine* e = force.engine();
+  ComputeOrient& c = orient_;
+  die_on(nepmi_orient_create(e, atom.number_of_atoms, c.mode, c.rc, c.nnn, c.degrees.data(), (int)c.degrees.size(), c.average ? 1 : 0,
+                             c.wl ? 1 : 0, c.wlhat ? 1 : 0, c.interval, &c.handle), "orientorder");
+  die_on(nepmi_orient_attach(e, c.handle), "orientorder");
+}
+
+void Run::orient_close()
+{
+  if (orient_.handle) {
+    die_on(nepmi_orient_detach(force.engine(), orient_.handle), "orient_detach");
+    nepmi_orient_destroy(orient_.handle);
+    orient_.handle = nullptr;
+  }
+}
+
+// the output half of OrientOrder::process (orientorder.cu:752-777): one block of the last sample, appended
+void Run::write_orient(int step)
+{
+  const ComputeOrient& c = orient_;
+  const int nd = (int)c.degrees.size(), ncol = nd * (1 + (c.wl ? 1 : 0) + (c.wlhat ? 1 : 0));
+  const int N = atom.number_of_atoms;
+  std::vector<double> last((size_t)N * ncol);
+  const int st = nepmi_orient_read(c.handle, last.data(), nullptr, nullptr, nullptr);
+  if (st == NEPMI_ERR_CAPACITY) {
+    std::printf("compute_orientorder: an atom has more than %d neighbours within the cutoff; the run ends here.\n    (%s)\n",
+                nepmi_orient_capacity(), nepmi_last_error());
+    std::fflush(stdout);
+    std::exit(1);
+  }
+  die_on(st, "orient_read");
+  FILE* fid = std::fopen("orientorder.out", "a");
+  if (!fid)
+    input_error("Cannot open orientorder.out for writing.");
+  std::fprintf(fid, "step = %d\n", step + 1);
+  std::fprintf(fid, "ql%d", c.degrees[0]);
+  for (int il = 1; il < nd; ++il)
+    std::fprintf(fid, " ql%d", c.degrees[(size_t)il]);
+  if (c.wl)
+    for (int il = 0; il < nd; ++il)
+      std::fprintf(fid, " wl%d", c.degrees[(size_t)il]);
+  if (c.wlhat)
+    for (int il = 0; il < nd; ++il)
+      std::fprintf(fid, " wlhat%d", c.degrees[(size_t)il]);
+  std::fprintf(fid, "\n");
+  for (int i = 0; i < N; ++i) {
+    for (int j = 0; j < ncol - 1; ++j)
+      std::fprintf(fid, "%f ", last[(size_t)i * ncol + j]);
+    std::fprintf(fid, "%f\n", last[(size_t)i * ncol + ncol - 1]);
+  }
+  std::fflush(fid);
+  std::fclose(fid);
+}
+
 // MSD::preprocess (msd.cu:205-267) / SDC::preprocess (sdc.cu:132-155): the correlator of this run, attached to the engine
 void Run::corr_open(ComputeCorr& c, int quantity, const char* name)
 {
@@ -954,6 +1093,12 @@ void Run::corr_sample_stepwise()
     const int st = nepmi_adf_sample(adf_.handle, atom.position_per_atom.data(), box.cpu_h, pbc);
     if (st != NEPMI_ERR_CAPACITY) // (write_adf reports an overflowed handle at the end of the segment)
       die_on(st, "adf_sample");
+  }
+  if (orient_.handle && corr_steps_ % orient_.interval == 0) {
+    const int pbc[3] = {box.pbc_x, box.pbc_y, box.pbc_z};
+    const int st = nepmi_orient_sample(orient_.handle, atom.position_per_atom.data(), box.cpu_h, pbc);
+    if (st != NEPMI_ERR_CAPACITY) // (write_orient reports an overflowed handle at the end of the segment)
+      die_on(st, "orient_sample");
   }
 }
 
@@ -1576,6 +1721,7 @@ void Run::perform_a_run()
   corr_open(dos_, 2, "DOS");
   rdf_open();
   adf_open();
+  orient_open();
   // target temperature of a temperature-dependent NEP (Run::parse_run, run.cu:679-681)
   // (integrate.temperature1/2 keep the values of the last ensemble that had them; an NVE-only input leaves them
   // uninitialised in the reference -- here they start at 300 K)
@@ -1627,6 +1773,8 @@ void Run::perform_a_run()
       upto(msd_.save_every); // msd_step<k>.out
     if (adf_.active)
       upto(adf_.interval); // a block of adf.out
+    if (orient_.active)
+      upto(orient_.interval); // a block of orientorder.out
     if (number_of_steps >= 10)
       upto(number_of_steps / 10); // progress lines
     if (correct_interval_ > 0) { // the correction precedes the steps 0, k, 2k, ...: a segment ends right before them
@@ -1657,6 +1805,8 @@ void Run::perform_a_run()
       write_msd(("msd_step" + std::to_string(done) + ".out").c_str());
     if (adf_.handle && done % adf_.interval == 0)
       write_adf(step); // ADF::process
+    if (orient_.handle && done % orient_.interval == 0)
+      write_orient(step); // OrientOrder::process
     if (number_of_steps >= 10 && (step + 1) % (number_of_steps / 10) == 0)
       std::printf("    %d steps completed.\n", step + 1);
   }
@@ -1676,6 +1826,7 @@ void Run::perform_a_run()
   corr_close(dos_);
   rdf_close();
   adf_close();
+  orient_close();
   const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   std::printf("Time used for this run = %g second.\n", sec);
   std::printf("Speed of this run = %g atom*step/second.\n", (double)N * number_of_steps / sec); // run.cu:325-326
@@ -1825,6 +1976,8 @@ void Run::perform_a_run_dist()
     input_error("compute_rdf is not available in multi-GPU runs.");
   if (adf_.active)
     input_error("compute_adf is not available in multi-GPU runs.");
+  if (orient_.active)
+    input_error("compute_orientorder is not available in multi-GPU runs.");
   const int N = atom.number_of_atoms;
   const bool root = par_.rank == 0;
   const int ens = ensemble == "nve" ? 0 : ensemble == "nvt_ber" ? 1 : ensemble == "nvt_nhc" ? 2 : ensemble == "nvt_bdp" ? 3

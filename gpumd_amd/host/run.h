@@ -80,6 +80,18 @@ struct ComputeAdf {
   nepmi_adf* handle = nullptr;       // of the run in progress
 };
 
+// OrientOrder (src/measure/orientorder.cuh): `compute_orientorder <interval> cutoff <rc> | nnn <k> <ndegrees> <l...> <average>
+// [<wl> [<wlhat>]]`.  The columns are libnepmi's (nepmi_orient_*), sampled inside the run loops; the run is cut at the sample
+// steps, where the host appends a block of the last sample to orientorder.out.
+struct ComputeOrient {
+  bool active = false;
+  int interval = 0, mode = 0, nnn = 0;
+  double rc = 6.0;
+  std::vector<int> degrees;
+  bool average = false, wl = false, wlhat = false;
+  nepmi_orient* handle = nullptr;    // of the run in progress
+};
+
 // One process per GPU (torchrun / mpirun style launch: RANK, WORLD_SIZE, LOCAL_RANK, MASTER_ADDR, MASTER_PORT or
 // OMPI_COMM_WORLD_*): the run is domain-decomposed by libnepmi's nepmi_dist_* driver (RCCL over xGMI when every
 // rank has its own GPU, TCP sockets otherwise); rank 0 writes the output files.
@@ -132,6 +144,10 @@ private:
   void adf_open();
   void adf_close();
   void write_adf(int step);
+  void parse_compute_orientorder(const std::vector<std::string>& p);
+  void orient_open();
+  void orient_close();
+  void write_orient(int step);
 
   bool check_only_;
   Parallel par_;
@@ -166,6 +182,7 @@ private:
   ComputeCorr msd_, sdc_, dos_;
   ComputeRdf rdf_;
   ComputeAdf adf_;
+  ComputeOrient orient_;
   int corr_steps_ = 0; // finished steps of the run in progress (the paths that step by hand sample on it)
   GPU_Vector<double> thermo; // 8 doubles
   std::vector<std::string> elements;

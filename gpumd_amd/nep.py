@@ -139,7 +139,9 @@ class NEP:
 
     def attach(self, corr):
         """The run_* methods sample `corr` (a Correlator, an RDF or an ADF of this engine) every corr.interval completed steps."""
-        if isinstance(corr, ADF):
+        if isinstance(corr, OrientOrder):
+            self._ck(self.lib.nepmi_orient_attach(self.handle, corr.handle))
+        elif isinstance(corr, ADF):
             self._ck(self.lib.nepmi_adf_attach(self.handle, corr.handle))
         elif isinstance(corr, RDF):
             self._ck(self.lib.nepmi_rdf_attach(self.handle, corr.handle))
@@ -147,7 +149,9 @@ class NEP:
             self._ck(self.lib.nepmi_corr_attach(self.handle, corr.handle))
 
     def detach(self, corr):
-        if isinstance(corr, ADF):
+        if isinstance(corr, OrientOrder):
+            self._ck(self.lib.nepmi_orient_detach(self.handle, corr.handle))
+        elif isinstance(corr, ADF):
             self._ck(self.lib.nepmi_adf_detach(self.handle, corr.handle))
         elif isinstance(corr, RDF):
             self._ck(self.lib.nepmi_rdf_detach(self.handle, corr.handle))
@@ -689,6 +693,66 @@ class ADF:
     def close(self):
         if getattr(self, "handle", None):
             self.lib.nepmi_adf_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        self.close()
+
+
+class OrientOrder:
+    """Steinhardt bond-orientational order per atom (nepmi_orient_*): `mode` is "cutoff" (`value` = the radius) or "nnn" (`value` =
+    the number of nearest neighbours, searched inside `rc_search`); `degrees`: 1 .. 8 values of l in 0 .. 12.  The columns of an
+    atom are ql[nd], then wl[nd] if `wl`, then wlhat[nd] if `wlhat`; `average` replaces q_lm by its mean over the atom and its
+    members (Lechner-Dellago) first.
+
+    Attach it to the engine (`engine.attach(o)`) and the run_* methods sample it on the device every `interval` steps; a host
+    that steps by hand calls `sample(pos, h, pbc)` with pos = [3N] f64 on the device.  `read()` -> (last [n, ncol], sum [n, ncol],
+    nn [n], num_samples), all in the caller's atom order.  A centre atom with more than `capacity` members inside the radius voids
+    the sample: `sample` and every later `read` raise with code -6."""
+
+    def __init__(self, engine, mode, value, degrees, average=False, wl=False, wlhat=False, interval=1, rc_search=6.0):
+        self.engine = engine
+        self.lib = engine.lib
+        if mode not in ("cutoff", "nnn"):
+            raise ValueError("mode: 'cutoff' or 'nnn'")
+        self.mode = mode
+        self.degrees = [int(l) for l in degrees]
+        self.nd = len(self.degrees)
+        self.average, self.wl, self.wlhat, self.interval = bool(average), bool(wl), bool(wlhat), int(interval)
+        self.ncol = self.nd * (1 + int(self.wl) + int(self.wlhat))
+        self.n = engine.n
+        rc = float(value) if mode == "cutoff" else float(rc_search)
+        nnn = 0 if mode == "cutoff" else int(value)
+        deg = (C.c_int * max(1, self.nd))(*self.degrees)
+        out = C.c_void_p()
+        _capi.check(self.lib, self.lib.nepmi_orient_create(engine.handle, engine.n, 0 if mode == "cutoff" else 1, rc, nnn, deg, self.nd,
+                                                           int(self.average), int(self.wl), int(self.wlhat), self.interval, C.byref(out)))
+        self.handle = out
+        if not hasattr(engine, "_correlators"):
+            engine._correlators = weakref.WeakSet()
+        engine._correlators.add(self)
+
+    @property
+    def capacity(self):
+        return int(self.lib.nepmi_orient_capacity())
+
+    def sample(self, pos, h, pbc):
+        _, hp = _h9(h)
+        _, pp = _pbc3(pbc)
+        _capi.check(self.lib, self.lib.nepmi_orient_sample(self.handle, NEP._ptr(pos), hp, pp))
+
+    def read(self):
+        last = np.zeros((self.n, self.ncol), dtype=np.float64)
+        total = np.zeros((self.n, self.ncol), dtype=np.float64)
+        nn = np.zeros(self.n, dtype=np.int32)
+        ns = C.c_int64(0)
+        _capi.check(self.lib, self.lib.nepmi_orient_read(self.handle, last.ctypes.data_as(_capi.c_dp), total.ctypes.data_as(_capi.c_dp),
+                                                         nn.ctypes.data_as(_capi.c_ip), C.byref(ns)))
+        return last, total, nn, int(ns.value)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.nepmi_orient_destroy(self.handle)
             self.handle = None
 
     def __del__(self):

@@ -240,6 +240,43 @@ int nepmi_adf_read(nepmi_adf* adf, uint64_t* counts_host, int64_t* num_samples);
 int nepmi_adf_set_lds_budget(nepmi_adf* adf, int64_t bytes);
 int nepmi_adf_form(nepmi_adf* adf);
 int nepmi_adf_capacity(void);
+/* ---- Steinhardt bond-orientational order sampled while the engine runs (replaces OrientOrder::process and its kernels,
+ *      src/measure/orientorder.cu:314-565, :637-750; the output, :752-777, belongs to the reader).
+ * Members of a centre atom i: the atoms a != i at the minimum-image d2 (apply_mic, double) with 0 < d2 < rc^2.  mode 1 (nnn)
+ * keeps, of those, the nnn members smallest in (d2, the caller's index); rc is then the search radius (the reference's 6.0).
+ * Per member, with d = sqrt(d2), rxy = sqrt(x^2 + y^2), c = z / d, s = rxy / d and e^{i phi} = (x + i y) / rxy (1 where
+ * rxy < 1e-15, :352-355): q_lm(i) = (1 / N_i) sum Y_lm, Y_lm with the prefactor and the phase of _polar_prefactor (:298-312) and
+ * compute_ql_step1 (:360-384), sin(theta) taken as s.  Only m >= 0 is kept: q_{l,-m} = (-1)^m conj(q_lm).
+ * average != 0: qbar_lm(i) = (q_lm(i) + sum_{j in members(i)} q_lm(j)) / (N_i + 1) replaces q_lm(i) (:470-514).
+ * Columns per atom, ncol = num_degrees (1 + wl + wlhat), in the reference's order (:401-468):
+ *   ql[nd]     q_l = sqrt(4 pi / (2l + 1) sum_m |q_lm|^2)
+ *   wl[nd]     if wl: sum CG Re(q_m1 q_m2 conj(q_{m1+m2})) / sqrt(2l + 1), CG as _init_clebsch_gordan builds it (:228-259)
+ *   wlhat[nd]  if wlhat: wl (sqrt(4 pi / (2l + 1)) / q_l)^3, and 0 where q_l <= 1e-15
+ * The object owns, on the device and in the caller's atom order,
+ *   last [n][ncol] double, the most recent sample;  sum [n][ncol] double, += last at every sample;  nn [n] int, the members used;
+ * and the sample counter.  Nothing is added with floating-point atomics: the same input gives the same bits.
+ * This is the reference's result except that (1) the membership test is in double (find_neighbor compares in float), (2) there is
+ * no silent cut at 200 neighbours: a sample in which a centre has more than nepmi_orient_capacity() members inside rc adds
+ * NOTHING, nepmi_orient_sample returns NEPMI_ERR_CAPACITY and so does every later nepmi_orient_read, (3) an atom with no member
+ * (mode 0) or with fewer than nnn members inside rc (mode 1) has nn = 0, all columns 0 and q_lm = 0 in its neighbours' averages
+ * (the reference prints NaN, or reads unwritten list entries), (4) ties in mode 1 are broken by the caller's index, (5) a
+ * neighbour at d2 == 0 is no member, (6) rc <= thickness / 2.5 of the sample's box is asked at EVERY sample, (7) degrees are
+ * 0 .. 12, at most 8 of them, repeats allowed.
+ *   _sample / _attach / _detach: as nepmi_adf_*; an attached handle samples after the ADF handles, last in the step.
+ *   _read: last_host, sum_host (HOST, [n][ncol]), nn_host (HOST, [n]), each may be NULL, and the samples so far.
+ * Errors (NEPMI_ERR_ARG): n is not the engine's, mode not 0 or 1, rc <= 0, nnn < 1 in mode 1, num_degrees outside 1 .. 8, a
+ * degree negative or above 12, sample_interval < 1, a handle attached twice or to another engine.
+ * Lifetime: as nepmi_adf -- destroy it BEFORE the engine it was created from. ---- */
+typedef struct nepmi_orient nepmi_orient;
+int nepmi_orient_create(
+  nepmi_engine* e, int64_t n, int mode, double rc, int nnn, const int* degrees, int num_degrees, int average, int wl, int wlhat,
+  int64_t sample_interval, nepmi_orient** out);
+void nepmi_orient_destroy(nepmi_orient* orient);
+int nepmi_orient_sample(nepmi_orient* orient, const double* pos, const double* h9, const int* pbc3);
+int nepmi_orient_attach(nepmi_engine* e, nepmi_orient* orient);
+int nepmi_orient_detach(nepmi_engine* e, nepmi_orient* orient);
+int nepmi_orient_read(nepmi_orient* orient, double* last_host, double* sum_host, int* nn_host, int64_t* num_samples);
+int nepmi_orient_capacity(void);
 /* The same call in two halves, so that a domain-decomposed host can overlap its ghost-position
  * exchange (the RCCL send/recv that replaces NEP_MULTIGPU's staged copies) with compute:
  *   _begin: the OWNED (level 2) entries of pos are final; ghost entries may still be in flight and
