@@ -1049,6 +1049,8 @@ int nepmi_engine_set_option(nepmi_engine* e, const char* name, double value)
     eng.set_lean_list_walks(iv != 0);
   else if (n == "angular_only_list_a")
     eng.set_angular_only_list_a(iv != 0);
+  else if (n == "rebuild_fast_pack")
+    eng.set_rebuild_fast_pack(iv != 0);
   else if (n == "fold_seam")
     eng.set_fold_seam(iv != 0);
   else if (n == "brick_force") {

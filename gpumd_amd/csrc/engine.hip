@@ -1598,6 +1598,21 @@ struct HipBackend {
     d2h(&most, word, sizeof(int));
     return most;
   }
+  // ... enqueued only: the caller reads flags[kFlagFoldRows] with its own look at the flags (engine option "rebuild_fast_pack")
+  void enqueue_fold_map(int64_t natoms, const BoxD& box, const Bufs& b, int wmax, int rows, unsigned* fmap)
+  {
+    int* word = b.flags + kFlagFoldRows;
+    NEPMI_HIP_CHECK(hipMemsetAsync(word, 0, sizeof(int), stream));
+    const FoldMapBody body{box, b, wmax, rows, fmap, word};
+    const int64_t grid = ((natoms + 255) / 256 + 7) / 8 * 8;
+    hipLaunchKernelGGL((nepmi_kernel<256, FoldMapBody>), dim3((unsigned)grid), dim3(256), 0, stream, body, natoms, nullptr);
+    NEPMI_HIP_CHECK(hipGetLastError());
+  }
+  // the bricks' statistics and window tables by one wavefront per brick (nep_bodies.h: TileStatsWaveBody)
+  void launch_tile_stats_wave(int slot, int64_t nbricks, const BoxD& box, const Bufs& b)
+  {
+    launch<64>(slot, nbricks * 64, TileStatsWaveBody{box, b});
+  }
 
   static constexpr bool kSplitLanes = true; // window kernels with several lanes per atom exist on this backend
   template <class Body>

@@ -1466,6 +1466,9 @@ private:
       b_.rmaskA = B::kHasScatter ? dalloc<unsigned>((size_t)b_.MAW * N) : nullptr;
       b_.rmaskB = B::kHasScatter ? dalloc<unsigned>((size_t)b_.MBW * N) : nullptr;
       b_.tmaskA = B::kHasScatter ? dalloc<unsigned>((size_t)b_.MAW * N) : nullptr;
+      // list B's type bits from the list builders (engine option "rebuild_fast_pack"): two-type models only
+      b_.MTB = (b_.MN_skin + 31) / 32;
+      b_.tmaskB = (B::kHasScatter && m.num_types == 2) ? dalloc<unsigned>((size_t)b_.MTB * N) : nullptr;
       b_.MA2 = 2 * ((b_.MN_ang + 3) / 4) + 2;
       const bool two = B::kHasScatter && m.num_types == 2;
       b_.acode2 = two ? dalloc<unsigned short>((size_t)b_.MA2 * N * 4) : nullptr;
@@ -1740,7 +1743,14 @@ private:
     be_.memset(b_.cell_count, 0, sizeof(int) * (ncell + 1));
     be_.memset(b_.cell_fill, 0, sizeof(int) * ncell);
     be_.memset(b_.cell_ghost, 0, sizeof(int) * ncell);
-    be_.memset(b_.flags + kFlagMaxSkin, 0, 2 * sizeof(int));
+    // engine option "rebuild_fast_pack" (this rebuild's value)
+    const bool fast = rebuild_fast_pack_;
+    static_assert(kFlagMaxAng == kFlagMaxSkin + 1 && kFlagMaxWindow == kFlagMaxAng + 1 && kFlagMaxCell == kFlagMaxWindow + 2, "adjacent flag words");
+    if (fast) { // the five maxima in one fill (nothing below writes the window words before their own place in the sequence)
+      be_.memset(b_.flags + kFlagMaxSkin, 0, 5 * sizeof(int));
+    } else {
+      be_.memset(b_.flags + kFlagMaxSkin, 0, 2 * sizeof(int));
+    }
     be_.memset(b_.flags + kFlagMoved, 0, sizeof(int)); // the rebuild this flag asked for is happening
     be_.memset(b_.flags + kFlagOutlier, 0, sizeof(int));
     be_.begin_region(kRegionRebuild);
@@ -1759,21 +1769,34 @@ private:
       be_.template launch<256>(kSlotMisc, N_, TypeFillBody{b_, model_.num_types});
     }
     // the bricks' statistics first (they need the cells only): they say whether the Verlet lists can be built from LDS windows
-    be_.memset(b_.flags + kFlagMaxWindow, 0, 3 * sizeof(int));
+    if (!fast)
+      be_.memset(b_.flags + kFlagMaxWindow, 0, 3 * sizeof(int));
     num_bricks_ = (int64_t)b_.gbx * b_.gby * b_.gbz;
     b_.brick_live = (b_.level && brick_live_buf_) ? brick_live_buf_ : nullptr;
     if (b_.level) {
       be_.memset(brick_live_buf_, 0, sizeof(int) * (size_t)(num_bricks_ + 1));
       be_.template launch<256>(kSlotMisc, N_, MarkGhostCellsBody{b_});
     }
-    be_.template launch<64>(kSlotMisc, num_bricks_, TileStatsBody{box_, b_});
+    bool wave_stats = false;
+    if constexpr (B::kHasScatter) { // (the device backend: a wavefront per brick)
+      if (fast) {
+        be_.launch_tile_stats_wave(kSlotMisc, num_bricks_, box_, b_);
+        wave_stats = true;
+      }
+    }
+    if (!wave_stats)
+      be_.template launch<64>(kSlotMisc, num_bricks_, TileStatsBody{box_, b_});
     be_.memset(b_.brick_flag + num_bricks_, 0, sizeof(int));
     be_.exclusive_scan(b_.brick_flag, num_bricks_ + 1, scan_scratch_);
     be_.template launch<64>(kSlotMisc, num_bricks_, BrickOrderBody{b_, num_bricks_});
     int flags[kNumFlags];
     bool build_in_windows = false;
+    bool looked = false; // the flags behind BrickOrderBody are on the host
+    // two-type shapes: the builder hands the neighbours' types over to the packing of the list words (Bufs::tbits)
+    b_.tbits = (fast && model_.kind == 0 && shape_ts() == 2 && b_.tmaskA && b_.tmaskB) ? 1 : 0;
     if (NEPMI_BUILD_WIN && use_tiles_ && model_.kind == 0 && b_.prec) {
       be_.d2h(flags, b_.flags, sizeof(flags));
+      looked = true;
       build_in_windows = flags[kFlagMaxCell] <= 127 && flags[kFlagMaxWindow] <= win_max_atoms() && !flags[kFlagOutlier];
       for (int d = 0; d < 3; ++d)
         if (box_.pbc[d] && nb[d] < 8)
@@ -1795,54 +1818,108 @@ private:
     if (model_.kind == 1 || b_.level) // (decomposed runs: eagerly -- their boundary bricks' radial pass may run on another stream)
       ensure_reverse_slots();
     be_.end_region(kRegionRebuild);
-    be_.d2h(flags, b_.flags, sizeof(flags));
-    check_overflow(flags);
-    num_boundary_bricks_ = flags[kFlagNumBoundary];
-    max_ang_rebuild_ = flags[kFlagMaxAng];
-    // LDS-window radial pass: unique window cells (>= 8 cells per periodic direction), 7-bit rank
-    // in cell, window fits the LDS budget
-    tile_ok_ = use_tiles_ && model_.kind == 0 && flags[kFlagMaxCell] <= 127 && flags[kFlagMaxWindow] <= win_max_atoms() &&
-               !flags[kFlagOutlier];
-    for (int d = 0; d < 3; ++d)
-      if (box_.pbc[d] && nb[d] < 8)
-        tile_ok_ = false;
-    if (std::getenv("NEPMI_DEBUG_REBUILD"))
-      std::fprintf(stderr, "nepmi rebuild: cells %d %d %d max_cell %d max_window %d (cap %d) max_brick %d outlier %d tiles %d -> tile_ok %d\n", nb[0], nb[1], nb[2],
-                   flags[kFlagMaxCell], flags[kFlagMaxWindow], win_max_atoms(), flags[kFlagMaxBrick], flags[kFlagOutlier], (int)use_tiles_, (int)tile_ok_);
-    win_.wmax = (flags[kFlagMaxWindow] + 63) / 64 * 64;
-    // static window layout of the one-lane window kernels: Verlet entries as LDS slots, four to a word
-    win2_ok_ = tile_ok_ && use_win2_ && b_.wtab != nullptr && win_.wmax < 65535;
-    if (win2_ok_) {
-      b_.wsent = win_.wmax;
-      aonly_built_ = aonly_list_a_active();
-      be_.template launch<128>(kSlotMisc, N_, PackCodesBody{b_, shape_ts() == 2 ? 2 : 1, (aonly_built_ && NEPMI_RW2_ABL != 4) ? 1 : 0});
+    // One look behind the builder ("rebuild_fast_pack"): what decides the window kernels (largest cell, fullest window, outliers)
+    // was final at the look behind BrickOrderBody, so the packing of the list words and the fold map are enqueued behind the
+    // builder at once, and ONE look at the end takes the overflow bits, the boundary bricks, the longest list A and the fold map's
+    // rows.  A capacity error leaves this call as it does with the three looks of option 0: same code, same message (the
+    // packing ORs the bit the builder has set, on lists clamped to their capacity), nothing of the engine's layout committed.
+    const bool one_look = fast && looked;
+    if (!one_look) {
       be_.d2h(flags, b_.flags, sizeof(flags));
       check_overflow(flags);
+      num_boundary_bricks_ = flags[kFlagNumBoundary];
+      max_ang_rebuild_ = flags[kFlagMaxAng];
     }
-    if (win2_ok_ && b_.aslot) {
+    // LDS-window radial pass: unique window cells (>= 8 cells per periodic direction), 7-bit rank
+    // in cell, window fits the LDS budget
+    bool tile_ok = use_tiles_ && model_.kind == 0 && flags[kFlagMaxCell] <= 127 && flags[kFlagMaxWindow] <= win_max_atoms() &&
+                   !flags[kFlagOutlier];
+    for (int d = 0; d < 3; ++d)
+      if (box_.pbc[d] && nb[d] < 8)
+        tile_ok = false;
+    if (std::getenv("NEPMI_DEBUG_REBUILD"))
+      std::fprintf(stderr, "nepmi rebuild: cells %d %d %d max_cell %d max_window %d (cap %d) max_brick %d outlier %d tiles %d -> tile_ok %d\n", nb[0], nb[1], nb[2],
+                   flags[kFlagMaxCell], flags[kFlagMaxWindow], win_max_atoms(), flags[kFlagMaxBrick], flags[kFlagOutlier], (int)use_tiles_, (int)tile_ok);
+    const int wmax = (flags[kFlagMaxWindow] + 63) / 64 * 64;
+    // static window layout of the one-lane window kernels: Verlet entries as LDS slots, four to a word
+    const bool win2_ok = tile_ok && use_win2_ && b_.wtab != nullptr && wmax < 65535;
+    const bool aonly = aonly_list_a_active();
+    if (!one_look) {
+      tile_ok_ = tile_ok;
+      win_.wmax = wmax;
+      win2_ok_ = win2_ok;
+    }
+    if (win2_ok) {
+      b_.wsent = wmax;
+      const int parts = shape_ts() == 2 ? 2 : 1, pack_aonly = (aonly && NEPMI_RW2_ABL != 4) ? 1 : 0;
+      if (b_.tbits)
+        be_.template launch<128>(kSlotMisc, N_, PackCodesTypedBody{b_, pack_aonly});
+      else
+        be_.template launch<128>(kSlotMisc, N_, PackCodesBody{b_, parts, pack_aonly});
+      if (!one_look) {
+        aonly_built_ = aonly;
+        be_.d2h(flags, b_.flags, sizeof(flags));
+        check_overflow(flags);
+      }
+    }
+    bool fold_ok = false, fold_enqueued = false;
+    if (win2_ok && b_.aslot) {
       // scatter-form force assembly: one halo row per brick (the window sums its workgroup leaves for ForceFoldBody, 12 bytes
       // per window slot) and, per atom, the table of the windows that hold it (nep_scatter.h: FoldMapBody)
-      const size_t need = (size_t)num_bricks_ * (size_t)win_.wmax * kHaloRowWords;
+      const size_t need = (size_t)num_bricks_ * (size_t)wmax * kHaloRowWords;
       if (need > halo_cap_) {
         dfree(halo_);
         halo_ = nullptr;
+        halo_cap_ = 0; // (an allocation that throws must not leave the old capacity behind)
         halo_ = dalloc<int>(need + need / 8);
         halo_cap_ = need + need / 8;
       }
       if (!fmap_)
         fmap_ = dalloc<unsigned>((size_t)fold_rows_ * cap_);
-      fold_ok_ = num_bricks_ < ((int64_t)1 << 19) && win_.wmax < (1 << 13);
-      if (fold_ok_) {
-        int most = be_.build_fold_map(N_, box_, b_, win_.wmax, fold_rows_, fmap_);
-        if (most > fold_rows_) { // (partly filled bricks next to a periodic face: a cell can lie in up to 27 windows)
-          fold_rows_ = most;
-          dfree(fmap_);
-          fmap_ = nullptr;
-          fmap_ = dalloc<unsigned>((size_t)fold_rows_ * cap_);
-          most = be_.build_fold_map(N_, box_, b_, win_.wmax, fold_rows_, fmap_);
+      fold_ok = num_bricks_ < ((int64_t)1 << 19) && wmax < (1 << 13);
+      if (fold_ok) {
+        if constexpr (B::kHasScatter) {
+          if (one_look) {
+            be_.enqueue_fold_map(N_, box_, b_, wmax, fold_rows_, fmap_);
+            fold_enqueued = true;
+          }
+        }
+        if (!fold_enqueued) {
+          if (one_look) { // (a backend without the enqueued form: the errors first, as ever)
+            be_.d2h(flags, b_.flags, sizeof(flags));
+            check_overflow(flags);
+          }
+          int most = be_.build_fold_map(N_, box_, b_, wmax, fold_rows_, fmap_);
+          if (most > fold_rows_) { // (partly filled bricks next to a periodic face: a cell can lie in up to 27 windows)
+            fold_rows_ = most;
+            dfree(fmap_);
+            fmap_ = nullptr;
+            fmap_ = dalloc<unsigned>((size_t)fold_rows_ * cap_);
+            most = be_.build_fold_map(N_, box_, b_, wmax, fold_rows_, fmap_);
+          }
         }
       }
     }
+    if (one_look) {
+      be_.d2h(flags, b_.flags, sizeof(flags));
+      check_overflow(flags);
+      num_boundary_bricks_ = flags[kFlagNumBoundary];
+      max_ang_rebuild_ = flags[kFlagMaxAng];
+      tile_ok_ = tile_ok;
+      win_.wmax = wmax;
+      win2_ok_ = win2_ok;
+      if (win2_ok)
+        aonly_built_ = aonly;
+      if (fold_enqueued && flags[kFlagFoldRows] > fold_rows_) { // (rare: the fold map needs more rows -- once more, as ever)
+        fold_rows_ = flags[kFlagFoldRows];
+        dfree(fmap_);
+        fmap_ = nullptr;
+        fmap_ = dalloc<unsigned>((size_t)fold_rows_ * cap_);
+        be_.build_fold_map(N_, box_, b_, wmax, fold_rows_, fmap_);
+      }
+    }
+    if (win2_ok && b_.aslot)
+      fold_ok_ = fold_ok;
     if (reverse_ghosts_ && b_.level) {
       // the rows a ghost would have written in forward mode are read by its neighbours' (and its own) force assembly: zero
       // = no contribution; owned atoms rewrite theirs every step
@@ -2269,6 +2346,7 @@ public:
     ang_flat_tables_ = o.ang_flat_tables_;
     lean_walks_ = o.lean_walks_;
     aonly_list_a_ = o.aonly_list_a_;
+    rebuild_fast_pack_ = o.rebuild_fast_pack_;
     fold_seam_ = o.fold_seam_;
     brick_force_ = o.brick_force_;
     loop_ctx_ = o.loop_ctx_;
@@ -2753,6 +2831,12 @@ public:
   // ... where it applies: two register-resident types, and no reader of the classic list words (the mask form of the per-step
   // radial list, option "radial_mask", walks list B's rows by their position)
   bool aonly_list_a_active() const { return aonly_list_a_ && shape_ts() == 2 && !use_rmask_; }
+  // 1 (default): the list rebuild without the work its result does not need -- the list builders hand the neighbours' types to the
+  // packing of the list words as bits (two-type shapes; nep_bodies.h: PackCodesTypedBody reads no PosQ), the bricks' statistics
+  // and window tables come from one wavefront per brick (TileStatsWaveBody), and the host looks at the flags once behind the
+  // builder instead of three times and a synchronisation; 0: the former bodies and looks.  The same words, integer for integer;
+  // takes effect at the next rebuild and asks for none.
+  void set_rebuild_fast_pack(bool on) { rebuild_fast_pack_ = on; }
   // ... the radial pass: shapes with packed per-type sums (one type: the clamp only; many types are not packed)
   template <class S>
   bool lean_radial() const
@@ -2914,6 +2998,7 @@ public:
     }
     s += (tile_ok_ && win2 && shape_ts() > 0 && lean_walks_) ? " list_walks=lean" : " list_walks=classic";
     s += (tile_ok_ && win2 && aonly_built_) ? " list_a=angular_only" : " list_a=classic";
+    s += rebuild_fast_pack_ ? (b_.tbits ? " rebuild=fast_pack(types_from_the_builder)" : " rebuild=fast_pack") : " rebuild=classic";
     s += (last_scatter_form_ && last_mask_form_)   ? " radial_list=inside_bits_over_the_verlet_words"
          : (last_scatter_form_ && last_sync_form_) ? " radial_list=wave_synchronous_words"
                                                    : " radial_list=compacted";
@@ -2997,6 +3082,8 @@ private:
   // set_angular_only_list_a; NEPMI_ANGULAR_ONLY_LIST_A=0 in the environment: the default of engines no caller can reach
   bool aonly_list_a_ = !(std::getenv("NEPMI_ANGULAR_ONLY_LIST_A") && std::atoi(std::getenv("NEPMI_ANGULAR_ONLY_LIST_A")) == 0);
   bool aonly_built_ = false; // the list words of the last rebuild hold list A's members in the streams
+  // set_rebuild_fast_pack; NEPMI_REBUILD_FAST_PACK=0 in the environment: the default of engines no caller can reach
+  bool rebuild_fast_pack_ = !(std::getenv("NEPMI_REBUILD_FAST_PACK") && std::atoi(std::getenv("NEPMI_REBUILD_FAST_PACK")) == 0);
   float* fused_img_flat_ = nullptr; // the flat-table image (the first form stays in fused_img_: the per-brick kernel reads it)
   size_t fused_img_flat_floats_ = 0;
   bool fused_img_flat_stale_ = true;

@@ -217,6 +217,12 @@ struct Bufs {
   unsigned* rmaskB;
   unsigned* tmaskA;
   int MAW, MBW;  // words per atom of rmaskA / tmaskA and of rmaskB
+  // Engine option "rebuild_fast_pack", two-type shapes: the list builders hand the neighbours' types over as bits in list order
+  // (they hold every accepted neighbour's record anyway) -- list A's into tmaskA, list B's into tmaskB[s >> 5][k] bit s & 31 --
+  // and the packing of the list words (PackCodesTypedBody) reads these words instead of one PosQ per entry
+  unsigned* tmaskB; // [MTB][N], MTB = ceil(MN_skin / 32); or nullptr
+  int MTB;
+  int tbits;        // 1: this rebuild's builder writes tmaskA / tmaskB
   // Two-type shapes, written at the rebuild for the mask-form force assembly: list A once more as two type-pure runs of words
   // (rows [0, wa0): entries of type 0, rows [wa0, wa0 + wa1): of type 1, padded with the sentinel slot), with the list-A index
   // of every entry (one byte each, 255 = padding) to find its bit in rmaskA; aseg2[k] = wa0 | wa1 << 8
@@ -724,6 +730,28 @@ struct GatherSortedBody {
   }
 };
 
+// The type bits of one Verlet list while a builder fills it (Bufs::tbits): entry s is bit s & 31 of row s >> 5, in list order; a
+// row is stored when it is full, the last one by finish()
+struct TypeBitRows {
+  unsigned cur = 0u;
+  NEPMI_HD void add(unsigned* rows, int64_t N, int64_t k, int s, bool other)
+  {
+    cur |= (other ? 1u : 0u) << (s & 31);
+    if ((s & 31) == 31) {
+      rows[(int64_t)(s >> 5) * N + k] = cur;
+      cur = 0u;
+    }
+  }
+  // n entries were added: the row they end in, and empty rows up to `nrows`
+  NEPMI_HD void finish(unsigned* rows, int64_t N, int64_t k, int n, int nrows)
+  {
+    for (int w = n >> 5; w < nrows; ++w) {
+      rows[(int64_t)w * N + k] = cur;
+      cur = 0u;
+    }
+  }
+};
+
 // gpu_find_neighbor_ON1 (neighbor.cu:85-162) in internal indices: because atoms are stored in
 // cell order, the members of cell c are simply the index range [cell_start[c], cell_start[c+1]).
 // The Verlet list (d < rc_r + skin) is written as two lists: A = also within rc_a + skin (the only
@@ -741,6 +769,7 @@ struct BuildListsBody {
     // periodic directions wrap (>= 5 bins guaranteed), non-periodic ones stop at the box edge
     const int lx = b.nbx > 1 ? 2 : 0, ly = b.nby > 1 ? 2 : 0, lz = b.nbz > 1 ? 2 : 0;
     int cnta = 0, cntb = 0;
+    TypeBitRows ta, tb; // (Bufs::tbits: the neighbours' types, from the PosQ the pair test has loaded)
     bool near_owned = false; // an owned atom within rc_a + skin: only then can an owned atom ask for this atom's f12
     for (int kz = -lz; kz <= lz; ++kz) {
       int z2 = cz + kz;
@@ -770,6 +799,8 @@ struct BuildListsBody {
                 if (cnta < b.MN_ang) {
                   b.nl_ang[(int64_t)cnta * N + k] = j;
                   b.code_ang[(int64_t)cnta * N + k] = code;
+                  if (b.tbits)
+                    ta.add(b.tmaskA, N, k, cnta, p2.type != 0);
                 }
                 ++cnta;
                 near_owned = near_owned || b.lvl[j] >= 2;
@@ -777,6 +808,8 @@ struct BuildListsBody {
                 if (cntb < b.MN_skin) {
                   b.nl_skin[(int64_t)cntb * N + k] = j;
                   b.code_skin[(int64_t)cntb * N + k] = code;
+                  if (b.tbits)
+                    tb.add(b.tmaskB, N, k, cntb, p2.type != 0);
                 }
                 ++cntb;
               }
@@ -794,6 +827,10 @@ struct BuildListsBody {
     }
     b.nn_ang[k] = cnta;
     b.nn_skin[k] = cntb;
+    if (b.tbits) { // every row of tmaskA, as PackCodesBody writes them; of tmaskB the row the list ends in
+      ta.finish(b.tmaskA, N, k, cnta, b.MAW);
+      tb.finish(b.tmaskB, N, k, cntb, (cntb >> 5) + 1 < b.MTB ? (cntb >> 5) + 1 : b.MTB);
+    }
     b.angf[k] = (b.lvl[k] >= 2 || (b.lvl[k] >= b.lvl_desc && near_owned)) ? 1 : 0;
   }
 };
@@ -971,6 +1008,87 @@ struct TileStatsBody {
   }
 };
 
+#if defined(__HIPCC__)
+// TileStatsBody by one wavefront per brick (engine option "rebuild_fast_pack"; launched with 64 work-items per brick, so that
+// work-item i is lane i & 63 of brick i >> 6): lane wz * 8 + wy takes the eight cells of its window row -- their counts and a
+// running sum inside the row -- and the 64 row totals are scanned across the wavefront, which is the serial body's running
+// offset (it walks wz, wy, wx in this order).  The same two integers per cell, the same maxima and ghost flag (one atomic per
+// brick and flag), where one lane per brick walked 512 cells with two dependent loads each.
+struct TileStatsWaveBody {
+  BoxD box;
+  Bufs b;
+  __device__ void operator()(int64_t i) const
+  {
+    const int64_t brick = i >> 6;
+    const int lane = (int)(i & 63);
+    const int wz = lane >> 3, wy = lane & 7;
+    const int bx = (int)(brick % b.gbx), by = (int)((brick / b.gbx) % b.gby), bz = (int)(brick / ((int64_t)b.gbx * b.gby));
+    int cy = 4 * by - 2 + wy, cz = 4 * bz - 2 + wz;
+    bool row_ok = true;
+    if (box.pbc[1]) cy = ((cy % b.nby) + b.nby) % b.nby; else row_ok = row_ok && cy >= 0 && cy < b.nby;
+    if (box.pbc[2]) cz = ((cz % b.nbz) + b.nbz) % b.nbz; else row_ok = row_ok && cz >= 0 && cz < b.nbz;
+    int first[8], cnt[8];
+    int total = 0, mxc = 0, ghost = 0;
+#pragma unroll
+    for (int wx = 0; wx < 8; ++wx) {
+      int cx = 4 * bx - 2 + wx;
+      bool ok = row_ok;
+      if (box.pbc[0]) cx = ((cx % b.nbx) + b.nbx) % b.nbx; else ok = ok && cx >= 0 && cx < b.nbx;
+      first[wx] = 0;
+      cnt[wx] = -1; // a window cell beyond an open face of the box
+      if (ok) {
+        const int c = cell_index(b, cx, cy, cz);
+        first[wx] = b.cell_count[c];
+        cnt[wx] = b.cell_count[c + 1] - first[wx];
+        total += cnt[wx];
+        mxc = cnt[wx] > mxc ? cnt[wx] : mxc;
+        ghost |= b.cell_ghost[c];
+      }
+    }
+    // exclusive scan of the row totals over the 64 lanes; the last lane's inclusive sum is the window's atom count
+    int incl = total;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int up = __shfl_up(incl, d, 64);
+      incl += lane >= d ? up : 0;
+    }
+    int win = incl - total;
+    if (b.wtab) {
+      int* t = b.wtab + ((int64_t)brick * 512 + lane * 8) * 2;
+#pragma unroll
+      for (int wx = 0; wx < 8; ++wx) {
+        if (cnt[wx] < 0) { // holds nothing (the running offset stays valid)
+          t[2 * wx] = 0;
+          t[2 * wx + 1] = win & 0xFFFF;
+        } else {
+          t[2 * wx] = first[wx];
+          t[2 * wx + 1] = (win & 0xFFFF) | (cnt[wx] << 16);
+          win += cnt[wx];
+        }
+      }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+      const int om = __shfl_xor(mxc, d, 64), og = __shfl_xor(ghost, d, 64);
+      mxc = om > mxc ? om : mxc;
+      ghost |= og;
+    }
+    if (lane == 63) {
+      b.brick_flag[brick] = ghost;
+      // (thousands of bricks raise the same three words: an atomic only where the word read is still smaller -- a stale read
+      // costs one atomic more, the maximum is the same)
+      const int nbr = b.cell_count[brick * 64 + 64] - b.cell_count[brick * 64];
+      if (incl > __atomic_load_n(&b.flags[kFlagMaxWindow], __ATOMIC_RELAXED))
+        NEPMI_ATOMIC_MAX(&b.flags[kFlagMaxWindow], incl);
+      if (nbr > __atomic_load_n(&b.flags[kFlagMaxBrick], __ATOMIC_RELAXED))
+        NEPMI_ATOMIC_MAX(&b.flags[kFlagMaxBrick], nbr);
+      if (mxc > __atomic_load_n(&b.flags[kFlagMaxCell], __ATOMIC_RELAXED))
+        NEPMI_ATOMIC_MAX(&b.flags[kFlagMaxCell], mxc);
+    }
+  }
+};
+#endif
+
 // Domain decomposition: cells that hold ghosts, and (after the in-place scan of brick_flag) the
 // brick order "interior first": a brick is interior when no ghost sits in its window, i.e. its
 // radial pass can run while the ghost positions of this step are still in flight.
@@ -1143,6 +1261,148 @@ struct PackCodesBody {
         put(slot_of(b.code_skin[(int64_t)s * N + k]));
       flush();
       wb = word - wa;
+    }
+    if (word > b.MN_wchunks || wa > 255 || wb > 255)
+      NEPMI_ATOMIC_OR(&b.flags[kFlagOverflow], 1);
+    b.wseg[k] = wa | (wb << 8);
+  }
+};
+
+// PackCodesBody for two-type shapes behind a builder that has handed the neighbours' types over (Bufs::tbits, engine option
+// "rebuild_fast_pack"): the same words -- wcode, wseg, acode2, aorig2, aseg2, sentinel padding, row order and overflow bits --
+// from the type bits of tmaskA / tmaskB, which are coalesced words of the atom's own rows, where PackCodesBody gathers one
+// 32-byte PosQ per entry through nl_ang / nl_skin (list A's up to three times).  It reads neither posq nor the index lists.
+// tmaskA is the builder's already.  Lists beyond the 256 places of the type mask look the bits up entry by entry.
+struct PackCodesTypedBody {
+  Bufs b;
+  int aonly;
+  NEPMI_HD void operator()(int64_t k) const
+  {
+    const int64_t N = b.N;
+    const int64_t brick = b.kcell[k] >> 6;
+    const int* tab = b.wtab + brick * 1024;
+    unsigned short* out = b.wcode + k * 4;
+    const int64_t row = N * 4; // halfwords per row of words
+    int word = 0, fill = 0;
+    unsigned long long cur = 0ull; // the word being filled, place u in bits 16 u: one 8-byte store per word, no indexed array
+    auto put = [&](unsigned short slot) {
+      cur |= (unsigned long long)slot << (16 * fill);
+      if (++fill == 4) {
+        if (word < b.MN_wchunks)
+          *reinterpret_cast<unsigned long long*>(out + (int64_t)word * row) = cur;
+        ++word;
+        fill = 0;
+        cur = 0ull;
+      }
+    };
+    auto flush = [&]() { // pad the segment to a whole word
+      while (fill != 0)
+        put((unsigned short)b.wsent);
+    };
+    auto slot_of = [&](unsigned code) { return (unsigned short)((tab[(code >> 7) * 2 + 1] & 0xFFFF) + (code & 127u)); };
+    const int na = b.nn_ang[k], nb = b.nn_skin[k];
+    for (int s = 0; s < na; ++s)
+      put(slot_of(b.code_ang[(int64_t)s * N + k]));
+    flush();
+    const int wa = word;
+    if (b.acode2) { // list A as two type-pure runs of words for the mask-form force assembly
+      int row2 = 0, wa0 = 0;
+      for (int t = 0; t < 2; ++t) {
+        unsigned long long sl = 0ull; // (place u in bits 16 u, as above)
+        unsigned ix = 0u;
+        int f2 = 0;
+        auto emit = [&]() {
+          if (row2 < b.MA2) {
+            *reinterpret_cast<unsigned long long*>(b.acode2 + ((int64_t)row2 * N + k) * 4) = sl;
+            b.aorig2[(int64_t)row2 * N + k] = ix;
+          }
+          ++row2;
+          f2 = 0;
+          ix = 0u;
+          sl = 0ull;
+        };
+        unsigned tw = 0u; // the row of tmaskA that holds entry s2
+        for (int s2 = 0; s2 < na; ++s2) {
+          if ((s2 & 31) == 0)
+            tw = b.tmaskA[(int64_t)(s2 >> 5) * N + k];
+          if ((((tw >> (s2 & 31)) & 1u) != 0u) != (t != 0))
+            continue;
+          sl |= (unsigned long long)slot_of(b.code_ang[(int64_t)s2 * N + k]) << (16 * f2);
+          ix |= (unsigned)(s2 < 255 ? s2 : 255) << (8 * f2);
+          if (++f2 == 4)
+            emit();
+        }
+        if (f2 != 0) {
+          for (; f2 < 4; ++f2) {
+            sl |= (unsigned long long)(unsigned short)b.wsent << (16 * f2);
+            ix |= 255u << (8 * f2);
+          }
+          emit();
+        }
+        if (t == 0)
+          wa0 = row2;
+      }
+      if (row2 > b.MA2 || na > 255)
+        NEPMI_ATOMIC_OR(&b.flags[kFlagOverflow], 1);
+      b.aseg2[k] = wa0 | ((row2 - wa0) << 8);
+    }
+    int wb = 0;
+    // two type-pure streams, word by word side by side, as PackCodesBody writes them (parts = 2)
+    const int n0 = aonly ? na : 0, nv = n0 + nb;
+    auto type_of = [&](int s) -> bool { // (long lists only)
+      const unsigned w = s < n0 ? b.tmaskA[(int64_t)(s >> 5) * N + k] : b.tmaskB[(int64_t)((s - n0) >> 5) * N + k];
+      return ((w >> ((s < n0 ? s : s - n0) & 31)) & 1u) != 0u;
+    };
+    auto code_of = [&](int s) -> unsigned {
+      return s < n0 ? b.code_ang[(int64_t)s * N + k] : b.code_skin[(int64_t)(s - n0) * N + k];
+    };
+    int s0 = 0, s1 = 0; // cursors over the source: next entry of type 0 / of type 1
+    // the types of the entries (bit s: entry s is not of type 0): the rows of the two lists, list B's shifted behind list A's
+    unsigned long long m0 = 0ull, m1 = 0ull, m2 = 0ull, m3 = 0ull; // (four scalars: no dynamically indexed register array)
+    const bool masked = nv <= 256;
+    if (masked) {
+      auto insert = [&](unsigned bits, int at) { // 32 bits at place `at` (bits beyond a list's end are zero)
+        const int w = at >> 6, sh = at & 63;
+        const unsigned long long lo = (unsigned long long)bits << sh;
+        const unsigned long long hi = sh > 32 ? (unsigned long long)bits >> (64 - sh) : 0ull;
+        m0 |= w == 0 ? lo : 0ull;
+        m1 |= w == 1 ? lo : (w == 0 ? hi : 0ull);
+        m2 |= w == 2 ? lo : (w == 1 ? hi : 0ull);
+        m3 |= w == 3 ? lo : (w == 2 ? hi : 0ull);
+      };
+      for (int w = 0; 32 * w < n0; ++w)
+        insert(b.tmaskA[(int64_t)w * N + k], 32 * w);
+      for (int w = 0; 32 * w < nb; ++w)
+        insert(b.tmaskB[(int64_t)w * N + k], n0 + 32 * w);
+    }
+    auto other = [&](int s) -> bool {
+      const int w = s >> 6;
+      const unsigned long long m = w == 0 ? m0 : (w == 1 ? m1 : (w == 2 ? m2 : m3));
+      return ((m >> (s & 63)) & 1ull) != 0ull;
+    };
+    auto next_of = [&](int& s, int want) -> int {
+      if (masked) {
+        while (s < nv && other(s) != (want != 0))
+          ++s;
+      } else {
+        while (s < nv && type_of(s) != (want != 0))
+          ++s;
+      }
+      return s < nv ? s++ : -1;
+    };
+    for (;;) {
+      int e0[4], e1[4];
+      for (int u = 0; u < 4; ++u)
+        e0[u] = next_of(s0, 0);
+      for (int u = 0; u < 4; ++u)
+        e1[u] = next_of(s1, 1);
+      if (e0[0] < 0 && e1[0] < 0)
+        break;
+      for (int u = 0; u < 4; ++u)
+        put(e0[u] >= 0 ? slot_of(code_of(e0[u])) : (unsigned short)b.wsent);
+      for (int u = 0; u < 4; ++u)
+        put(e1[u] >= 0 ? slot_of(code_of(e1[u])) : (unsigned short)b.wsent);
+      ++wb;
     }
     if (word > b.MN_wchunks || wa > 255 || wb > 255)
       NEPMI_ATOMIC_OR(&b.flags[kFlagOverflow], 1);

@@ -333,6 +333,7 @@ struct BuildListsWinBody {
     const float unit2 = b.wg.unit2, band = b.wg.band;
     const int lx = b.nbx > 1 ? 2 : 0, ly = b.nby > 1 ? 2 : 0, lz = b.nbz > 1 ? 2 : 0;
     int cnta = 0, cntb = 0;
+    TypeBitRows ta, tb; // (Bufs::tbits: the neighbours' types, from the LDS record of every accepted slot)
     bool near_owned = false;
     // a row of the sweep (fixed kz, ky; kx = -lx .. lx) is ONE range of window slots: consecutive window cells hold consecutive
     // slots.  One loop per row instead of one per cell: a wavefront runs the longest of its lanes' loops, and the longest of 64
@@ -385,12 +386,16 @@ struct BuildListsWinBody {
               cell_lo = cell_hi;
               cell_hi = woff[wc + 1];
             }
-            const int j = (int)((unsigned)wrec[s].w & (unsigned)kIdxMask);
+            const unsigned jw = (unsigned)wrec[s].w;
+            const int j = (int)(jw & (unsigned)kIdxMask);
+            const bool other = (jw >> kIdxBits) != 0u;
             const unsigned short code = (unsigned short)((wc << 7) | ((s - cell_lo) & 127));
             if ((ma >> i2) & 1u) {
               if (cnta < b.MN_ang) {
                 b.nl_ang[(int64_t)cnta * N + k] = j;
                 b.code_ang[(int64_t)cnta * N + k] = code;
+                if (b.tbits)
+                  ta.add(b.tmaskA, N, k, cnta, other);
               }
               ++cnta;
               near_owned = near_owned || b.lvl[j] >= 2;
@@ -398,6 +403,8 @@ struct BuildListsWinBody {
               if (cntb < b.MN_skin) {
                 b.nl_skin[(int64_t)cntb * N + k] = j;
                 b.code_skin[(int64_t)cntb * N + k] = code;
+                if (b.tbits)
+                  tb.add(b.tmaskB, N, k, cntb, other);
               }
               ++cntb;
             }
@@ -414,6 +421,10 @@ struct BuildListsWinBody {
     }
     b.nn_ang[k] = cnta;
     b.nn_skin[k] = cntb;
+    if (b.tbits) { // (the rows BuildListsBody writes)
+      ta.finish(b.tmaskA, N, k, cnta, b.MAW);
+      tb.finish(b.tmaskB, N, k, cntb, (cntb >> 5) + 1 < b.MTB ? (cntb >> 5) + 1 : b.MTB);
+    }
     b.angf[k] = (b.lvl[k] >= 2 || (b.lvl[k] >= b.lvl_desc && near_owned)) ? 1 : 0;
   }
 };

@@ -440,6 +440,12 @@ class NEP:
         asks for."""
         self.set_option("angular_only_list_a", 1 if on else 0)
 
+    def set_rebuild_fast_pack(self, on=True):
+        """the list rebuild with the neighbours' types handed from the list builder to the packing of the list words, the
+        bricks' statistics by a wavefront per brick and one host look behind the builder (default), or the former kernels and
+        looks (option "rebuild_fast_pack"); the same list words, bit-identical results.  Takes effect at the next rebuild."""
+        self.set_option("rebuild_fast_pack", 1 if on else 0)
+
     def set_fold_seam(self, on=True):
         """single-domain NVE run loops in the scatter form: the fold of the window sums inside the integrator pass behind it
         (default), or as a launch of its own (option "fold_seam"); bit-identical results (a window sum too large for the seam

@@ -725,6 +725,18 @@ int nepmi_engine_set_virial_mode(nepmi_engine* e, int mode);
  *       nepmi_engine_describe says list_a=classic -- for one-type, many-type and run-time shapes and while "radial_mask" is set
  *       (the mask form walks list B's rows by their position).  NEPMI_ANGULAR_ONLY_LIST_A=0 in the environment sets the default
  *       of engines no caller reaches.
+ *   "rebuild_fast_pack": value = 1 (default) -- the list rebuild without the work its result does not need: on two-type compiled
+ *       shapes the list builders, which hold every accepted neighbour's record, hand its type to the packing of the list words as
+ *       one bit per entry in list order, so that the packing reads coalesced words of the atom's own rows and no longer one
+ *       position record per entry through the index lists; the bricks' statistics and window tables are formed by one wavefront
+ *       per brick (a segmented prefix sum over the 512 window cells) instead of one work-item per brick; and the host looks at
+ *       the device flags once behind the list builder instead of three times and a stream synchronisation (the packing and the
+ *       fold map are enqueued at once: what decides them was final before the builder ran).  0: the former kernels and looks.
+ *       Every list word, table entry, maximum and flag is the same integer either way, a capacity error leaves the same call with
+ *       the same code and message: results are equal under numpy.array_equal (tests/test_rebuild_fast_pack.py).  Applies to
+ *       decomposed engines as to single-domain ones; takes effect at the next rebuild and asks for none.  nepmi_engine_describe
+ *       says rebuild=fast_pack / rebuild=classic.  NEPMI_REBUILD_FAST_PACK=0 in the environment sets the default of engines no
+ *       caller reaches.
  *   "fold_seam": Single-domain NVE run loops whose force assembly takes the scatter form: value = 1 (default) -- the fold of the
  *       window sums (one atom's entries of the up to eight brick windows that hold it) runs inside the integrator pass behind it
  *       (second half-kick of the step, and on a step that neither records thermo data nor ends the call the first half-kick, drift,
