@@ -32,4 +32,4 @@ def load_library():
     return _lib
 
 
-from .nep import ADF, NEP, RDF, Correlator, Model, OrientOrder  # noqa: E402,F401
+from .nep import ADF, ARDF, NEP, RDF, Correlator, Model, OrientOrder  # noqa: E402,F401

@@ -133,6 +133,14 @@ SYMBOLS = {
     "nepmi_rdf_read": (C.c_int, [VP, C.POINTER(C.c_uint64), c_dp, C.POINTER(c_i64)]),
     "nepmi_rdf_set_lds_budget": (C.c_int, [VP, c_i64]),
     "nepmi_rdf_form": (C.c_int, [VP]),
+    "nepmi_ardf_create": (C.c_int, [VP, c_i64, C.c_double, C.c_int, C.c_int, c_i64, c_ip, C.c_int, C.c_int, c_ip, C.POINTER(VP)]),
+    "nepmi_ardf_destroy": (None, [VP]),
+    "nepmi_ardf_sample": (C.c_int, [VP, VP, c_dp, c_ip]),
+    "nepmi_ardf_attach": (C.c_int, [VP, VP]),
+    "nepmi_ardf_detach": (C.c_int, [VP, VP]),
+    "nepmi_ardf_read": (C.c_int, [VP, C.POINTER(C.c_uint64), c_dp, C.POINTER(c_i64)]),
+    "nepmi_ardf_set_lds_budget": (C.c_int, [VP, c_i64]),
+    "nepmi_ardf_form": (C.c_int, [VP]),
     "nepmi_adf_create": (C.c_int, [VP, c_i64, C.c_int, c_i64, VP, C.c_int, c_ip, C.c_int, C.POINTER(VP)]),
     "nepmi_adf_destroy": (None, [VP]),
     "nepmi_adf_sample": (C.c_int, [VP, VP, c_dp, c_ip]),

@@ -40,6 +40,11 @@ struct nepmi_rdf {
   nepmi::RdfT<NepmiBackend>* r;
 };
 
+struct nepmi_ardf {
+  const nepmi_api* api;
+  nepmi::ArdfT<NepmiBackend>* r;
+};
+
 struct nepmi_adf {
   const nepmi_api* api;
   nepmi::AdfT<NepmiBackend>* a;
@@ -854,6 +859,89 @@ int nepmi_rdf_form(nepmi_rdf* r)
 {
   if (!r)
     return fail(NEPMI_ERR_ARG, "null rdf handle");
+  return r->r->form();
+}
+
+int nepmi_ardf_create(
+  nepmi_engine* e, int64_t n, double rc, int num_r_bins, int num_theta_bins, int64_t sample_interval, const int* type_of_atom,
+  int num_types, int num_pairs, const int* pair_types, nepmi_ardf** out)
+{
+  if (!e || !out)
+    return fail(NEPMI_ERR_ARG, "null argument");
+  *out = nullptr;
+  nepmi_ardf* r = new nepmi_ardf();
+  r->api = NEPMI_SELF_API;
+  r->r = nullptr;
+  const int st = guarded([&] {
+    if (n != e->e->num_atoms())
+      throw nepmi::EngineError{NEPMI_ERR_ARG, "ardf: n is not the engine's number of atoms"};
+    r->r = new nepmi::ArdfT<NepmiBackend>(e->e->backend(), n, rc, num_r_bins, num_theta_bins, sample_interval, type_of_atom, num_types,
+                                          num_pairs, pair_types);
+  });
+  if (st != NEPMI_OK) {
+    delete r;
+    return st;
+  }
+  *out = r;
+  return NEPMI_OK;
+}
+
+void nepmi_ardf_destroy(nepmi_ardf* r)
+{
+  if (!r)
+    return;
+  if (r->r && r->r->attached_to)
+    guarded([&] { static_cast<nepmi::EngineT<NepmiBackend>*>(r->r->attached_to)->ardf_detach(r->r); });
+  guarded([&] { delete r->r; });
+  delete r;
+}
+
+int nepmi_ardf_sample(nepmi_ardf* r, const double* pos, const double* h9, const int* pbc3)
+{
+  if (!r || !pos || !h9 || !pbc3)
+    return fail(NEPMI_ERR_ARG, "null argument");
+  return guarded([&] {
+    nepmi::BoxD box;
+    nepmi::box_from_h9(h9, pbc3, box);
+    r->r->sample_now(pos, box);
+  });
+}
+
+int nepmi_ardf_attach(nepmi_engine* e, nepmi_ardf* r)
+{
+  if (!e || !r)
+    return fail(NEPMI_ERR_ARG, "null argument");
+  if (r->api != e->api)
+    return fail(NEPMI_ERR_ARG, "ardf: created from an engine of another kernel library");
+  return guarded([&] { e->e->ardf_attach(r->r); });
+}
+
+int nepmi_ardf_detach(nepmi_engine* e, nepmi_ardf* r)
+{
+  if (!e || !r)
+    return fail(NEPMI_ERR_ARG, "null argument");
+  return guarded([&] { e->e->ardf_detach(r->r); });
+}
+
+int nepmi_ardf_read(nepmi_ardf* r, uint64_t* counts_host, double* vsum_host, int64_t* num_samples)
+{
+  if (!r)
+    return fail(NEPMI_ERR_ARG, "null ardf handle");
+  return guarded([&] { r->r->read(reinterpret_cast<unsigned long long*>(counts_host), vsum_host, num_samples); });
+}
+
+int nepmi_ardf_set_lds_budget(nepmi_ardf* r, int64_t bytes)
+{
+  if (!r)
+    return fail(NEPMI_ERR_ARG, "null ardf handle");
+  r->r->set_lds_budget(bytes);
+  return NEPMI_OK;
+}
+
+int nepmi_ardf_form(nepmi_ardf* r)
+{
+  if (!r)
+    return fail(NEPMI_ERR_ARG, "null ardf handle");
   return r->r->form();
 }
 

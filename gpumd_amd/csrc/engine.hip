@@ -1290,6 +1290,33 @@ struct HipBackend {
       launch_adf_triplets_form<false>(a, n, words, lds_bytes);
   }
 
+  // pair histogram of one angular-RDF sample (nep_ardf.h) in the form the handle's counted rule chose; the cell starts come from
+  // launch_adf_scan
+  static constexpr bool kHasArdf = true;
+  template <bool LDSHIST>
+  void launch_ardf_pairs_form(const ArdfArgs& a, int64_t nblocks, int words, size_t lds_bytes)
+  {
+    const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(kRdfLanesPerCu / kRdfLanes, (int64_t)(160 * 1024 / lds_bytes))); // workgroups that share a CU
+    const unsigned grid = (unsigned)std::min<int64_t>(nblocks, per_cu * 256);
+    if (lds_bytes > 64 * 1024)
+      NEPMI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&nepmi_ardf_pairs<LDSHIST>),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    hipLaunchKernelGGL((nepmi_ardf_pairs<LDSHIST>), dim3(grid), dim3(kRdfLanes), lds_bytes, stream, a, nblocks, words, frozen);
+    NEPMI_HIP_CHECK(hipGetLastError());
+  }
+  void launch_ardf_pairs(const ArdfArgs& a, int64_t nblocks, bool lds_hist, int words)
+  {
+    if (nblocks <= 0)
+      return;
+    const size_t lds_bytes = (size_t)kRdfFixedLds + (lds_hist ? 4 * (size_t)words : 0);
+    if (lds_bytes > (size_t)kRdfLdsPerWorkgroup)
+      throw std::runtime_error("ardf: the LDS table does not fit");
+    if (lds_hist)
+      launch_ardf_pairs_form<true>(a, nblocks, words, lds_bytes);
+    else
+      launch_ardf_pairs_form<false>(a, nblocks, words, lds_bytes);
+  }
+
   // q_lm of one orientational-order sample (nep_orient.h): the first pass, or the neighbour average over its rows
   static constexpr bool kHasOrient = true;
   void launch_orient_qlm(const OrientArgs& a, int64_t n, bool average)

@@ -10,6 +10,7 @@
 #include "nep_corr.h"
 #include "nep_rdf.h"
 #include "nep_adf.h"
+#include "nep_ardf.h"
 #include "nep_orient.h"
 #include "nep_model.h"
 #include "nep_window.h"
@@ -726,6 +727,7 @@ public:
     } loop_ctx(*this);
     corr_check(n);
     rdf_check(n);
+    ardf_check(n);
     adf_check(n);
     orient_check(n);
     if ((is_small_box(box) && model_.kind == 0) || (stepwise_loops_ && (ens == kLan || ens == kBao))) {
@@ -1012,6 +1014,8 @@ public:
         corr_sample_step(step, b_.ui, b_.vi, N_, b_.perm, frozen);
       if (!rdfs_.empty()) // (positions only as well; the box is the one this step ends with: under npt_ber the scaled one)
         rdf_sample_step(step, nullptr, b_.posq, b_.perm, N_, box_, frozen);
+      if (!ardfs_.empty()) // (after the RDF handles, before the ADF ones; positions only, the step's box)
+        ardf_sample_step(step, nullptr, b_.posq, b_.perm, N_, box_, frozen);
       if (!adfs_.empty()) // (last of the step's launches; positions only, the step's box)
         adf_sample_step(step, nullptr, b_.posq, b_.perm, N_, box_, frozen);
       if (!orients_.empty()) // (after the ADF handles: the last of the step's launches)
@@ -1020,6 +1024,7 @@ public:
     }
     corr_advance(nsteps);
     rdf_advance(nsteps);
+    ardf_advance(nsteps);
     adf_advance(nsteps);
     orient_advance(nsteps);
     num_compute = compute0 + nsteps;
@@ -1126,6 +1131,8 @@ public:
         corr_sample_step(step, unwrapped_, vel, n, nullptr, nullptr);
       if (!rdfs_.empty())
         rdf_sample_step(step, pos, nullptr, nullptr, n, box, nullptr);
+      if (!ardfs_.empty())
+        ardf_sample_step(step, pos, nullptr, nullptr, n, box, nullptr);
       if (!adfs_.empty())
         adf_sample_step(step, pos, nullptr, nullptr, n, box, nullptr);
       if (!orients_.empty())
@@ -1134,6 +1141,7 @@ public:
     if (nsteps > 0) {
       corr_advance(nsteps);
       rdf_advance(nsteps);
+      ardf_advance(nsteps);
       adf_advance(nsteps);
       orient_advance(nsteps);
     }
@@ -1261,6 +1269,24 @@ private:
       r->advance(nsteps);
   }
   std::vector<RdfT<B>*> rdfs_;
+  void ardf_check(int64_t n) const
+  {
+    for (const ArdfT<B>* r : ardfs_)
+      if (r->n() != n)
+        throw EngineError{-4, "an attached angular-RDF handle was created for another number of atoms"};
+  }
+  void ardf_sample_step(int64_t step, const double* pos, const PosQ* posq, const int* perm, int64_t n, const BoxD& box, const int* frozen)
+  {
+    for (ArdfT<B>* r : ardfs_)
+      if (r->sample_after(step))
+        r->sample(pos, posq, perm, n, box, frozen);
+  }
+  void ardf_advance(int64_t nsteps)
+  {
+    for (ArdfT<B>* r : ardfs_)
+      r->advance(nsteps);
+  }
+  std::vector<ArdfT<B>*> ardfs_;
   void adf_check(int64_t n) const
   {
     for (const AdfT<B>* r : adfs_)
@@ -2245,6 +2271,29 @@ public:
         return;
       }
     throw EngineError{-4, "rdf: not attached to this engine"};
+  }
+  // angular-RDF handles (nep_ardf.h): the rules of the RDF handles above; they sample after them and before the ADF handles
+  void ardf_attach(ArdfT<B>* r)
+  {
+    if (r->n() > cap_)
+      throw EngineError{-4, "ardf: more atoms than the engine's capacity"};
+    for (ArdfT<B>* o : ardfs_)
+      if (o == r)
+        throw EngineError{-4, "ardf: already attached"};
+    if (r->attached_to)
+      throw EngineError{-4, "ardf: attached to another engine"};
+    ardfs_.push_back(r);
+    r->attached_to = this;
+  }
+  void ardf_detach(ArdfT<B>* r)
+  {
+    for (size_t i = 0; i < ardfs_.size(); ++i)
+      if (ardfs_[i] == r) {
+        ardfs_.erase(ardfs_.begin() + i);
+        r->attached_to = nullptr;
+        return;
+      }
+    throw EngineError{-4, "ardf: not attached to this engine"};
   }
   // ADF handles (nep_adf.h): the rules of the RDF handles above; they sample after them
   void adf_attach(AdfT<B>* r)

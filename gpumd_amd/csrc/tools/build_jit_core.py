@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.dirname(HERE)
 FILES = ["engine.hip", "nep_model.cpp", "transport_tcp.cpp", "engine_impl.h", "capi_impl.h", "capi_jit.h", "capi_dispatch.inc",
          "dist_bodies.h", "dist_impl.h", "dist_capi_impl.h", "nep_dev.h", "nep_bodies.h", "nep_window.h", "nep_scatter.h",
-         "nep_fused.h", "nep_highl.h", "nep_highl_tables.h", "nep_invariants_extra.h", "nep_md.h", "nep_corr.h", "nep_rdf.h", "nep_adf.h", "nep_orient.h", "nep_model.h", "tersoff_bodies.h",
+         "nep_fused.h", "nep_highl.h", "nep_highl_tables.h", "nep_invariants_extra.h", "nep_md.h", "nep_corr.h", "nep_rdf.h", "nep_adf.h", "nep_ardf.h", "nep_orient.h", "nep_model.h", "tersoff_bodies.h",
          "../../include/nepmi.h"]  # = capi_jit.h: source_files()
 
 

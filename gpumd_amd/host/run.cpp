@@ -438,6 +438,8 @@ void Run::parse_one_keyword(const std::vector<std::string>& p)
     parse_compute_dos(p);
   } else if (k == "compute_rdf") {
     parse_compute_rdf(p);
+  } else if (k == "compute_angular_rdf") {
+    parse_compute_angular_rdf(p);
   } else if (k == "compute_adf") {
     parse_compute_adf(p);
   } else if (k == "compute_orientorder") {
@@ -462,6 +464,7 @@ void Run::parse_one_keyword(const std::vector<std::string>& p)
     sdc_ = ComputeCorr();
     dos_ = ComputeCorr();
     rdf_ = ComputeRdf();
+    ardf_ = ComputeArdf();
     adf_ = ComputeAdf();
     orient_ = ComputeOrient();
   } else {
@@ -706,6 +709,150 @@ void Run::write_rdf()
       for (int b = a; b < T; ++b, ++q)
         std::fprintf(fid, " %.5f", (a == b ? 2.0 : 1.0) * vsum[(size_t)q * nb + bin] / ((double)c.num_atoms[a] * c.num_atoms[b] * dV) / num_repeats);
     std::fprintf(fid, "\n");
+  }
+  std::fflush(fid);
+  std::fclose(fid);
+}
+
+// AngularRDF::parse (angular_rdf.cu:662-757), with its messages.  Ours: a type index equal to the number of types is refused (the
+// reference's test is >), a trailing `atom` group needs its two numbers (the reference reads past its parameters), and the
+// library's limit of 1024 theta bins.
+void Run::parse_compute_angular_rdf(const std::vector<std::string>& p)
+{
+  std::printf("Compute Angular RDF.\n");
+  ComputeArdf c;
+  c.active = true;
+  if (p.size() < 5)
+    input_error("compute_angular_rdf should have at least 4 parameters.");
+  if (p.size() > 23)
+    input_error("compute_angular_rdf has too many parameters.");
+  if (!is_valid_real(p[1], &c.rc))
+    input_error("radial cutoff should be a number.");
+  if (c.rc <= 0)
+    input_error("radial cutoff should be positive.");
+  {
+    const double* h = box.cpu_h; // columns a, b, c
+    const double a[3] = {h[0], h[3], h[6]}, b[3] = {h[1], h[4], h[7]}, cc[3] = {h[2], h[5], h[8]};
+    auto area = [](const double* u, const double* v) {
+      const double s1 = u[1] * v[2] - u[2] * v[1], s2 = u[2] * v[0] - u[0] * v[2], s3 = u[0] * v[1] - u[1] * v[0];
+      return std::sqrt(s1 * s1 + s2 * s2 + s3 * s3);
+    };
+    const double volume = box.get_volume();
+    const double thickness_half[3] = {volume / area(b, cc) / 2.5, volume / area(cc, a) / 2.5, volume / area(a, b) / 2.5};
+    if (c.rc > thickness_half[0] || c.rc > thickness_half[1] || c.rc > thickness_half[2])
+      input_error("The box has a thickness < 2.5 RDF radial cutoffs in a periodic direction.\n"
+                  "                Please increase the periodic direction(s).");
+  }
+  std::printf("    radial cutoff %g.\n", c.rc);
+  if (!is_valid_int(p[2], &c.num_r_bins))
+    input_error("number of bins should be an integer.");
+  if (c.num_r_bins <= 20)
+    input_error("A larger nbins is recommended.");
+  if (c.num_r_bins > 500)
+    input_error("A smaller nbins is recommended.");
+  std::printf("    radial cutoff will be divided into %d bins.\n", c.num_r_bins);
+  if (!is_valid_int(p[3], &c.num_theta_bins))
+    input_error("number of theta bins should be an integer.");
+  if (c.num_theta_bins <= 20)
+    input_error("A larger ntheta is recommended.");
+  if (c.num_theta_bins > 1024)
+    input_error("number of theta bins should be at most 1024.");
+  std::printf("    theta cutoff will be divided into %d bins.\n", c.num_theta_bins);
+  if (!is_valid_int(p[4], &c.interval))
+    input_error("interval step per sample should be an integer.");
+  if (c.interval <= 0)
+    input_error("interval step per sample should be positive.");
+  std::printf("    Angular RDF sample interval is %d step.\n", c.interval);
+  const int number_of_types = (int)elements.size();
+  for (size_t k = 5; k < p.size(); k += 3) {
+    if (p[k] != "atom")
+      input_error("Unrecognized argument in compute_angular_rdf.");
+    if (k + 2 >= p.size())
+      input_error("an atom group of compute_angular_rdf should have 2 type indices.");
+    int id1 = 0, id2 = 0;
+    if (!is_valid_int(p[k + 1], &id1))
+      input_error("atom type index1 should be an integer.");
+    if (id1 < 0)
+      input_error("atom type index1 should be non-negative.");
+    if (id1 >= number_of_types)
+      input_error("atom type index1 should be less than number of atomic types.");
+    if (!is_valid_int(p[k + 2], &id2))
+      input_error("atom type index2 should be an integer.");
+    if (id2 < 0)
+      input_error("atom type index2 should be non-negative.");
+    if (id2 >= number_of_types)
+      input_error("atom type index1 should be less than number of atomic types."); // (sic: angular_rdf.cu:751)
+    c.pair_types.push_back(id1);
+    c.pair_types.push_back(id2);
+  }
+  ardf_ = c;
+}
+
+// AngularRDF::preprocess (angular_rdf.cu:440-504): the handle of this run, attached to the engine
+void Run::ardf_open()
+{
+  if (!ardf_.active)
+    return;
+  nepmi_engine* e = force.engine();
+  const int num_pairs = (int)ardf_.pair_types.size() / 2;
+  die_on(nepmi_ardf_create(e, atom.number_of_atoms, ardf_.rc, ardf_.num_r_bins, ardf_.num_theta_bins, ardf_.interval, atom.cpu_type.data(),
+                           (int)elements.size(), num_pairs, num_pairs ? ardf_.pair_types.data() : nullptr, &ardf_.handle),
+         "angular RDF");
+  die_on(nepmi_ardf_attach(e, ardf_.handle), "angular RDF");
+}
+
+void Run::ardf_close()
+{
+  if (ardf_.handle) {
+    die_on(nepmi_ardf_detach(force.engine(), ardf_.handle), "ardf_detach");
+    nepmi_ardf_destroy(ardf_.handle);
+    ardf_.handle = nullptr;
+  }
+}
+
+// AngularRDF::postprocess (angular_rdf.cu:585-660) on the integer sums: the reference adds 1 / (N rho bv) per ordered pair of a
+// sample, i.e. V / (N^2 bv) (column (a, a): V / (N_a^2 bv); (a, b): V / (N_a N_b bv) from both ends, halved when printed)
+void Run::write_angular_rdf()
+{
+  const ComputeArdf& c = ardf_;
+  const int C = 1 + (int)c.pair_types.size() / 2, R = c.num_r_bins, T = c.num_theta_bins;
+  std::vector<double> vsum((size_t)C * R * T);
+  int64_t samples = 0;
+  die_on(nepmi_ardf_read(c.handle, nullptr, vsum.data(), &samples), "ardf_read");
+  FILE* fid = std::fopen("angular_rdf.out", "a");
+  if (!fid)
+    input_error("Cannot open angular_rdf.out for writing.");
+  std::vector<double> type_size(elements.size(), 0.0); // atom.cpu_type_size
+  for (int t : atom.cpu_type)
+    if (t >= 0 && t < (int)type_size.size())
+      type_size[t] += 1.0;
+  std::fprintf(fid, "#radius theta");
+  for (int a = 0; a < C; ++a) {
+    if (a == 0)
+      std::fprintf(fid, " total");
+    else
+      std::fprintf(fid, " type_%d_%d", c.pair_types[2 * (a - 1)], c.pair_types[2 * (a - 1) + 1]);
+  }
+  std::fprintf(fid, "\n");
+  const int num_repeats = number_of_steps / c.interval;
+  const double PI = 3.14159265358979, rdf_PI = 3.14159265358979323846; // (the reference's two constants, angular_rdf.cu:61, common.cuh:20)
+  const double r_step = c.rc / R, theta_step = 2 * PI / T, N = (double)atom.number_of_atoms;
+  for (int nc = 0; nc < R; ++nc) {
+    const double radial = nc * r_step + r_step / 2;
+    const double r_low = radial - r_step / 2, r_up = radial + r_step / 2;
+    const double shell_volume = 4.0 / 3.0 * rdf_PI * (r_up * r_up * r_up - r_low * r_low * r_low);
+    for (int tc = 0; tc < T; ++tc) {
+      const double theta = -PI + tc * theta_step + theta_step / 2;
+      const double theta_low = theta - theta_step / 2, theta_up = theta + theta_step / 2;
+      const double bin_volume = (theta_up - theta_low) / (2 * rdf_PI) * shell_volume;
+      std::fprintf(fid, "%.5f %.5f", radial, theta);
+      for (int a = 0; a < C; ++a) {
+        const double v = vsum[((size_t)a * R + nc) * T + tc];
+        const double w = a == 0 ? N * N : type_size[c.pair_types[2 * (a - 1)]] * type_size[c.pair_types[2 * (a - 1) + 1]];
+        std::fprintf(fid, " %.5f", v == 0.0 ? 0.0 : v / (w * bin_volume) / num_repeats);
+      }
+      std::fprintf(fid, "\n");
+    }
   }
   std::fflush(fid);
   std::fclose(fid);
@@ -1087,6 +1234,10 @@ void Run::corr_sample_stepwise()
   if (rdf_.handle && corr_steps_ % rdf_.interval == 0) {
     const int pbc[3] = {box.pbc_x, box.pbc_y, box.pbc_z};
     die_on(nepmi_rdf_sample(rdf_.handle, atom.position_per_atom.data(), box.cpu_h, pbc), "rdf_sample");
+  }
+  if (ardf_.handle && corr_steps_ % ardf_.interval == 0) {
+    const int pbc[3] = {box.pbc_x, box.pbc_y, box.pbc_z};
+    die_on(nepmi_ardf_sample(ardf_.handle, atom.position_per_atom.data(), box.cpu_h, pbc), "ardf_sample");
   }
   if (adf_.handle && corr_steps_ % adf_.interval == 0) {
     const int pbc[3] = {box.pbc_x, box.pbc_y, box.pbc_z};
@@ -1720,6 +1871,7 @@ void Run::perform_a_run()
   corr_open(sdc_, 1, "SDC");
   corr_open(dos_, 2, "DOS");
   rdf_open();
+  ardf_open();
   adf_open();
   orient_open();
   // target temperature of a temperature-dependent NEP (Run::parse_run, run.cu:679-681)
@@ -1821,10 +1973,13 @@ void Run::perform_a_run()
     write_dos();
   if (rdf_.handle)
     write_rdf(); // RDF::postprocess
+  if (ardf_.handle)
+    write_angular_rdf(); // AngularRDF::postprocess
   corr_close(msd_);
   corr_close(sdc_);
   corr_close(dos_);
   rdf_close();
+  ardf_close();
   adf_close();
   orient_close();
   const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -1974,6 +2129,8 @@ void Run::perform_a_run_dist()
     input_error("compute_dos is not available in multi-GPU runs.");
   if (rdf_.active)
     input_error("compute_rdf is not available in multi-GPU runs.");
+  if (ardf_.active)
+    input_error("compute_angular_rdf is not available in multi-GPU runs.");
   if (adf_.active)
     input_error("compute_adf is not available in multi-GPU runs.");
   if (orient_.active)

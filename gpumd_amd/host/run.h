@@ -69,6 +69,17 @@ struct ComputeRdf {
   nepmi_rdf* handle = nullptr;       // of the run in progress
 };
 
+// Angular RDF (src/measure/angular_rdf.cuh): `compute_angular_rdf <rc> <r_bins> <theta_bins> <interval> [atom <i> <j>]...`, up to
+// six `atom` groups.  The pair counts are libnepmi's (nepmi_ardf_*), sampled inside the run loops; the normalisation and
+// angular_rdf.out are the host's.
+struct ComputeArdf {
+  bool active = false;
+  double rc = 0.0;
+  int num_r_bins = 0, num_theta_bins = 0, interval = 0;
+  std::vector<int> pair_types;       // [pairs][2], types in the potential's order
+  nepmi_ardf* handle = nullptr;      // of the run in progress
+};
+
 // ADF (src/measure/adf.cuh): `compute_adf <interval> <num_bins> <rc_min> <rc_max>` or `compute_adf <interval> <num_bins>
 // (<itype> <jtype> <ktype> <rc_min_j> <rc_max_j> <rc_min_k> <rc_max_k>)+`.  The triplet counts are libnepmi's (nepmi_adf_*),
 // sampled inside the run loops; the run is cut at the sample steps, where the host appends a block to adf.out.
@@ -140,6 +151,10 @@ private:
   void rdf_open();
   void rdf_close();
   void write_rdf();
+  void parse_compute_angular_rdf(const std::vector<std::string>& p);
+  void ardf_open();
+  void ardf_close();
+  void write_angular_rdf();
   void parse_compute_adf(const std::vector<std::string>& p);
   void adf_open();
   void adf_close();
@@ -181,6 +196,7 @@ private:
   ActiveLearning active_;
   ComputeCorr msd_, sdc_, dos_;
   ComputeRdf rdf_;
+  ComputeArdf ardf_;
   ComputeAdf adf_;
   ComputeOrient orient_;
   int corr_steps_ = 0; // finished steps of the run in progress (the paths that step by hand sample on it)

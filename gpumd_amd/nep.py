@@ -139,7 +139,9 @@ class NEP:
 
     def attach(self, corr):
         """The run_* methods sample `corr` (a Correlator, an RDF or an ADF of this engine) every corr.interval completed steps."""
-        if isinstance(corr, OrientOrder):
+        if isinstance(corr, ARDF):
+            self._ck(self.lib.nepmi_ardf_attach(self.handle, corr.handle))
+        elif isinstance(corr, OrientOrder):
             self._ck(self.lib.nepmi_orient_attach(self.handle, corr.handle))
         elif isinstance(corr, ADF):
             self._ck(self.lib.nepmi_adf_attach(self.handle, corr.handle))
@@ -149,7 +151,9 @@ class NEP:
             self._ck(self.lib.nepmi_corr_attach(self.handle, corr.handle))
 
     def detach(self, corr):
-        if isinstance(corr, OrientOrder):
+        if isinstance(corr, ARDF):
+            self._ck(self.lib.nepmi_ardf_detach(self.handle, corr.handle))
+        elif isinstance(corr, OrientOrder):
             self._ck(self.lib.nepmi_orient_detach(self.handle, corr.handle))
         elif isinstance(corr, ADF):
             self._ck(self.lib.nepmi_adf_detach(self.handle, corr.handle))
@@ -625,6 +629,111 @@ class RDF:
 
     def __del__(self):
         self.close()
+
+
+class ARDF:
+    """Angular-resolved RDF as integer pair counts (nepmi_ardf_*): `num_r_bins` bins up to `rc`, `num_theta_bins` bins of the
+    azimuth of the pair vector in the xy plane; column 0 is the total, then one column per ordered type pair of `pairs`
+    (up to six (a, b)).  `type_of_atom`: n ints in the caller's atom order, 0 .. num_types - 1 (not needed without pairs).
+
+    `attach()` and the engine's run_* methods sample it on the device every `interval` steps; a host that steps by hand calls
+    `sample(pos, h, pbc)` with pos = [3N] f64 on the device.  `read()` -> (counts [C, R, T] uint64, vsum [C, R, T] = sum over
+    the samples of count * volume, num_samples); `g(n_of_type)` normalises as the reference's angular_rdf.out.
+    `set_lds_budget(bytes)` moves the threshold between the two forms of the pair kernel; `form` is 1 (tables in LDS) or 2."""
+
+    def __init__(self, engine, rc, num_r_bins, num_theta_bins, interval, type_of_atom=None, num_types=1, pairs=()):
+        self.engine = engine
+        self.lib = engine.lib
+        self.rc, self.num_r_bins, self.num_theta_bins = float(rc), int(num_r_bins), int(num_theta_bins)
+        self.interval, self.num_types = int(interval), int(num_types)
+        self.pairs = [(int(a), int(b)) for a, b in pairs]
+        self.num_columns = 1 + len(self.pairs)
+        tp = None
+        if type_of_atom is not None:
+            t = np.ascontiguousarray(np.asarray(type_of_atom), dtype=np.int32)
+            if t.shape != (engine.n,):
+                raise ValueError("type_of_atom: one int per atom")
+            tp = t.ctypes.data_as(_capi.c_ip)
+        pt = np.ascontiguousarray(np.asarray(self.pairs, dtype=np.int32).reshape(-1))
+        out = C.c_void_p()
+        _capi.check(self.lib, self.lib.nepmi_ardf_create(engine.handle, engine.n, self.rc, self.num_r_bins, self.num_theta_bins,
+                                                         self.interval, tp, self.num_types, len(self.pairs),
+                                                         pt.ctypes.data_as(_capi.c_ip) if len(self.pairs) else None, C.byref(out)))
+        self.handle = out
+        if not hasattr(engine, "_correlators"):
+            engine._correlators = weakref.WeakSet()
+        engine._correlators.add(self)
+
+    @property
+    def form(self):
+        return _capi.check(self.lib, self.lib.nepmi_ardf_form(self.handle))
+
+    def set_lds_budget(self, nbytes):
+        _capi.check(self.lib, self.lib.nepmi_ardf_set_lds_budget(self.handle, int(nbytes)))
+
+    def attach(self):
+        self.engine.attach(self)
+
+    def detach(self):
+        self.engine.detach(self)
+
+    def sample(self, pos, h, pbc):
+        _, hp = _h9(h)
+        _, pp = _pbc3(pbc)
+        _capi.check(self.lib, self.lib.nepmi_ardf_sample(self.handle, NEP._ptr(pos), hp, pp))
+
+    def read(self):
+        shape = (self.num_columns, self.num_r_bins, self.num_theta_bins)
+        counts = np.zeros(shape, dtype=np.uint64)
+        vsum = np.zeros(shape)
+        ns = C.c_int64(0)
+        _capi.check(self.lib, self.lib.nepmi_ardf_read(self.handle, counts.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                       vsum.ctypes.data_as(_capi.c_dp), C.byref(ns)))
+        return counts, vsum, int(ns.value)
+
+    def g(self, num_atoms_of_type, num_repeats=None):
+        """-> (r [R], theta [T], g [C, R, T]): angular_rdf.cu:124-129 and :605-644 on the integer sums; num_repeats defaults to
+        the samples taken."""
+        _, vsum, ns = self.read()
+        return ardf_normalise(vsum, self.rc, self.pairs, num_atoms_of_type, ns if num_repeats is None else num_repeats)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.nepmi_ardf_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        self.close()
+
+
+ARDF_PI = 3.14159265358979  # the reference's PI (utilities/common.cuh): the bin edges and the printed angles are formed with it
+
+
+def ardf_edges(rc, num_r_bins, num_theta_bins):
+    """-> (r, lo, up [R], theta, theta_up [T]): the bin centres and edges as the reference forms them (angular_rdf.cu:116-121,
+    :459-478)"""
+    dr = rc / num_r_bins
+    r = np.array([w * dr + dr / 2 for w in range(num_r_bins)])
+    step = 2 * ARDF_PI / num_theta_bins
+    th = np.array([-ARDF_PI + t * step + step / 2 for t in range(num_theta_bins)])
+    return r, r - dr / 2, r + dr / 2, th, th + step / 2
+
+
+def ardf_normalise(vsum, rc, pairs, num_atoms_of_type, num_repeats):
+    """The one normalisation of the angular-RDF sums: bv = D / (2 pi) * 4 pi / 3 (up^3 - lo^3); total = vsum / (N^2 bv S),
+    (a, a) = vsum / (N_a^2 bv S), (a, b) = vsum / (N_a N_b bv S)."""
+    vsum = np.asarray(vsum, dtype=np.float64)
+    na = np.asarray(num_atoms_of_type, dtype=np.float64)
+    _, R, T = vsum.shape
+    r, lo, up, th, _ = ardf_edges(rc, R, T)
+    bv = (1.0 / T) * (4.0 / 3.0 * np.pi * (up ** 3 - lo ** 3))
+    g = np.zeros_like(vsum)
+    S = float(num_repeats)
+    for c in range(vsum.shape[0]):
+        w = na.sum() ** 2 if c == 0 else na[pairs[c - 1][0]] * na[pairs[c - 1][1]]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            g[c] = vsum[c] / (w * bv[:, None] * S)
+    return r, th, g
 
 
 class AdfRow(C.Structure):

@@ -201,6 +201,49 @@ int nepmi_rdf_detach(nepmi_engine* e, nepmi_rdf* rdf);
 int nepmi_rdf_read(nepmi_rdf* rdf, uint64_t* counts_host, double* vsum_host, int64_t* num_samples);
 int nepmi_rdf_set_lds_budget(nepmi_rdf* rdf, int64_t bytes);
 int nepmi_rdf_form(nepmi_rdf* rdf);
+/* ---- Angular-resolved RDF sampled while the engine runs (replaces AngularRDF::process / gpu_find_angular_rdf_ON1,
+ *      src/measure/angular_rdf.cu:37-300, :506-583; the normalisation and the output, :585-660, belong to the reader): the pair
+ *      distribution resolved in the distance r and in the azimuth of the pair vector in the xy plane.
+ * A handle has C = 1 + num_pairs columns (column 0 "total", then the ordered type pairs (a_k, b_k) of pair_types, 0 .. 6 of them),
+ * R = num_r_bins radial bins (1 .. 500) and T = num_theta_bins azimuth bins (1 .. 1024).  An ordered pair i -> j, i != j, has
+ * the minimum-image vector d = r_j - r_i in double, d2 = |d|^2, theta = atan2(d_y, d_x); it counts if 0 < d2 <= rc^2, in
+ *   the radial bin w with lo_w^2 < d2 <= up_w^2, edges as the reference forms them (:116-118, :459-469): radial[w] = w dr + dr / 2,
+ *     lo = radial[w] - dr / 2, up = radial[w] + dr / 2, dr = rc / R;
+ *   the azimuth bin: the smallest t with theta <= up_t, clamped to T - 1; up_t = (-PI + t D + D / 2) + D / 2, D = 2 PI / T, as at
+ *     :119-121, :474-478 (PI: the reference's 3.14159265358979).  The direction -x lands in bin T - 1 whatever the sign of its zero.
+ *   Column 0 counts every ordered pair (an unordered pair adds two counts, at theta and at the reversed direction); a column
+ *   (a, a) every ordered pair of two type-a atoms; a column (a, b), a != b, each unordered a-b pair ONCE, in the direction from
+ *   the a atom to the b atom (the reference adds that direction from both ends and halves it when it prints, :239-296, :642-644).
+ * The object owns, on the device,
+ *   counts [C][R][T] unsigned 64-bit,
+ *   vsum   [C][R][T] double: += count of the sample * volume of the sample's box (the reference normalises with each sample's
+ *          own volume, :538-543),
+ * and the sample counter.  Integer sums: exact, independent of the order of the atoms and of the additions, the same bits run
+ * after run; nothing is divided on the device.  With bv = D / (2 pi) * 4 pi / 3 (up^3 - lo^3) and S samples the reference's
+ * columns are  total = vsum / (N^2 bv S),  (a, a) = vsum / (N_a^2 bv S),  (a, b) = vsum / (N_a N_b bv S).
+ * Deviations from the reference: every counted pair lands in exactly ONE bin (the reference tests every bin and
+ * may count a theta at an edge zero times or twice; -x may count nowhere there); integer sums instead of per-atom doubles; a
+ * type index equal to num_types is refused (the reference's test is >).
+ * type_of_atom: HOST array of n ints in the caller's atom order, 0 .. num_types - 1; may be NULL when num_pairs == 0.
+ * pair_types: HOST [num_pairs][2].
+ *   _sample, _attach, _read, _set_lds_budget / _form: as nepmi_rdf_*; attached handles sample after the RDF handles and before
+ *            the ADF handles.  The pair kernel keeps every workgroup's table [C][R][T] (32-bit) in LDS while it fits in `bytes`
+ *            beside the staging buffers (default: half a CU's 160 KB) and adds straight to the global table otherwise.
+ * Errors (NEPMI_ERR_ARG): n is not the engine's, rc <= 0, bins out of range, num_pairs outside 0 .. 6, a type outside
+ * 0 .. num_types - 1, rc above thickness / 2.5 of the sample's box in a periodic direction (asked at EVERY sample), a handle
+ * attached twice or to another engine.
+ * Lifetime: as a correlator's -- destroy it BEFORE the engine it was created from. ---- */
+typedef struct nepmi_ardf nepmi_ardf;
+int nepmi_ardf_create(
+  nepmi_engine* e, int64_t n, double rc, int num_r_bins, int num_theta_bins, int64_t sample_interval, const int* type_of_atom,
+  int num_types, int num_pairs, const int* pair_types, nepmi_ardf** out);
+void nepmi_ardf_destroy(nepmi_ardf* ardf);
+int nepmi_ardf_sample(nepmi_ardf* ardf, const double* pos, const double* h9, const int* pbc3);
+int nepmi_ardf_attach(nepmi_engine* e, nepmi_ardf* ardf);
+int nepmi_ardf_detach(nepmi_engine* e, nepmi_ardf* ardf);
+int nepmi_ardf_read(nepmi_ardf* ardf, uint64_t* counts_host, double* vsum_host, int64_t* num_samples);
+int nepmi_ardf_set_lds_budget(nepmi_ardf* ardf, int64_t bytes);
+int nepmi_ardf_form(nepmi_ardf* ardf);
 /* ---- Angular distribution function sampled while the engine runs (replaces ADF::process / gpu_find_adf_global / _local,
  *      src/measure/adf.cu:37-176, :237-310; the normalisation and the output, adf.cu:315-350, belong to the reader).
  * A handle holds num_rows rows (1 .. 32) and num_bins bins (1 .. 4096).  A row is (itype, jtype, ktype, [rmin_j, rmax_j),
